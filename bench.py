@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the hot path (BASELINE.json): patient-trajectories/s of the
 batched 6-state DP5(4) solve (ODE + 4x64 MLP residual, fp32, T = 241 grid points = 240 intervals).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -550,6 +550,33 @@ def data_side(dev, B, cpu=True):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, sol, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """Write what the caller of the timed path receives -- the solution y [B,T,6] (fp32) and the per-trajectory status, accepted
+    steps and RHS evaluations (as float64: exact for int32) -- as out_dir/<name>.npy.  When all of it would exceed max_bytes, a
+    fixed, seeded sample of trajectories (the same rows in every run) is written instead, with its row indices in rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    y = sol.y.detach().float().cpu().numpy()
+    per = {"status": sol.status, "nsteps": sol.nsteps, "nfev": sol.nfev}
+    per = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in per.items()}
+    B = y.shape[0]
+    row_bytes = y[0].nbytes + 8 * len(per) + 8
+    budget = max_bytes - 1024                            # the .npy headers (128 B each)
+    rows = None
+    if B * row_bytes > budget:
+        n = max(1, budget // row_bytes)
+        rows = np.sort(np.random.default_rng(seed).choice(B, size=n, replace=False))
+        y = y[rows]
+        per = {k: v[rows] for k, v in per.items()}
+    np.save(os.path.join(out_dir, "y.npy"), np.ascontiguousarray(y))
+    for k, v in per.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+    if rows is not None:
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -575,7 +602,11 @@ def main():
     ap.add_argument("--total-patients", type=int, default=0, help="N > 1: shard this many patients over the ranks with "
                     "hode.train.shard_bounds (uneven shards allowed) instead of --patients-per-gpu each")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, default) | gloo (rehearsal: ranks may share one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "returned (y, status, nsteps, nfev of rank 0's shard) as DIR/<name>.npy, for output-by-output comparison of builds")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -658,6 +689,8 @@ def main():
     nsteps = float(sol.nsteps.double().sum())
     ok = int((sol.status == 0).sum())
     value = B_total * args.steps / wall
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, sol)
 
     # ------------------------------------------------------------------ secondary: z-scored regime
     # what GlucoseDataset(normalize=True) actually feeds (train/train_hybrid.py:139): x0 ~ N(0,1)^6

@@ -152,3 +152,30 @@ print("rccl one-rank ok")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0 and "rccl one-rank ok" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR` times K steps, reports ms_per_step, and writes what the timed forward solve
+    returned for its synthetic cohort (seeded: the same inputs every run) -- checked against a solve of those inputs here."""
+    import bench
+    import hode
+    B = 128
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--patients-per-gpu", str(B),
+           "--no-cpu-baseline", "--no-train", "--no-vi", "--no-generic", "--no-data-side", "--no-sobol", "--no-class-path",
+           "--no-zscore", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert sorted(os.listdir(out_dir)) == ["nfev.npy", "nsteps.npy", "status.npy", "y.npy"]
+    dev = torch.device("cuda")
+    x0, t, meal, tv = (v.to(dev) for v in bench.synth_cohort(B, 1000))
+    sol = hode.solve_fwd(x0, t, meal, tv, None, bench.ODE_DEFAULT.to(dev), bench.synth_weights(0).to(dev), 64, 4, rtol=1e-6, atol=1e-8)
+    y = np.load(out_dir / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (B, 241, 6)
+    assert np.allclose(y, sol.y.cpu().numpy(), rtol=1e-6, atol=1e-7)
+    assert np.array_equal(np.load(out_dir / "status.npy"), sol.status.cpu().numpy().astype(np.float64))
+    assert np.array_equal(np.load(out_dir / "nsteps.npy"), sol.nsteps.cpu().numpy().astype(np.float64))

@@ -85,3 +85,33 @@ def test_saltelli_design_of_the_sobol_leg():
     assert np.allclose(bench.sobol_outputs(y), want, rtol=1e-13)
     x0, t, meal, tvns = bench.sobol_inputs()
     assert x0.tolist() == [5.0, 60.0, 80.0, 0.0, 0.0, 1.0] and t.shape == (61,) and float(meal[0, 6]) == 75.0 and float(meal.sum()) == 75.0
+
+
+def test_dump_outputs_writes_the_solution_and_samples_fixed_rows_when_too_large(tmp_path):
+    """bench.py --dump-outputs: y (fp32) and status / nsteps / nfev (fp64) as <name>.npy; above the byte cap a seeded sample of
+    trajectories (the same rows every run) is written, with their indices in rows.npy."""
+    import types
+
+    import numpy as np
+    import torch
+    B, T = 50, 7
+    g = torch.Generator().manual_seed(0)
+    sol = types.SimpleNamespace(y=torch.randn(B, T, 6, generator=g), status=torch.arange(B, dtype=torch.int32) % 3,
+                                nsteps=torch.arange(B, dtype=torch.int32) + 100, nfev=torch.arange(B, dtype=torch.int32) * 6 + 2)
+    full = tmp_path / "full"
+    bench.dump_outputs(str(full), sol)
+    assert sorted(os.listdir(full)) == ["nfev.npy", "nsteps.npy", "status.npy", "y.npy"]
+    y = np.load(full / "y.npy")
+    assert y.dtype == np.float32 and np.array_equal(y, sol.y.numpy())
+    for k in ("status", "nsteps", "nfev"):
+        v = np.load(full / f"{k}.npy")
+        assert v.dtype == np.float64 and np.array_equal(v, getattr(sol, k).numpy())
+    cap = 10 * (T * 6 * 4 + 32) + 1024                                # room for 10 trajectories + the .npy headers
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), sol, max_bytes=cap)
+    bench.dump_outputs(str(b), sol, max_bytes=cap)
+    rows = np.load(a / "rows.npy").astype(np.int64)
+    assert len(rows) == 10 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(b / "rows.npy"))
+    assert sum(os.path.getsize(a / f) for f in os.listdir(a)) <= cap
+    assert np.array_equal(np.load(a / "y.npy"), sol.y.numpy()[rows])
+    assert np.array_equal(np.load(a / "nfev.npy"), sol.nfev.numpy()[rows].astype(np.float64))

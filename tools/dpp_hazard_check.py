@@ -34,8 +34,9 @@ def regs(tok):
 
 
 total = 0
+tmp = tempfile.TemporaryDirectory(prefix="hz_")     # private: a fixed name in the shared temp dir can belong to another user
 for src in srcs:
-    out = os.path.join(tempfile.gettempdir(), "hz_" + os.path.basename(src) + ".s")
+    out = os.path.join(tmp.name, os.path.basename(src) + ".s")
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "--cuda-device-only", "-S",
                     "-Wno-unused-function", *flags, src if os.path.isabs(src) else os.path.join(ROOT, src), "-o", out], check=True,
                    stderr=subprocess.DEVNULL)
