@@ -68,8 +68,10 @@ template <typename R>
 int solve_bwd(void *stream, int B, int T, const R *t, int t_batched, const R *meal, int meal_mode, const R *tvns,
               int tvns_mode, const R *gd, int gd_mode, const R *ode_p, const R *nn_p, int n_sets, int H, int L,
               int method, int max_steps, const int32_t *nsteps, const int32_t *status, void *tape, const R *gy,
-              R *gx0, R *gnn, R *gode)
+              R *gx0, R *gnn, R *gode, R *gmeal = nullptr, R *gtvns = nullptr, R *ggd = nullptr)
 {
+    // a gradient is only defined for an input that is there (mode 1 or 2)
+    if ((gmeal && meal_mode == 0) || (gtvns && tvns_mode == 0) || (ggd && gd_mode == 0)) return HODE_EINVAL;
     if (B == 0 && T >= 1) return HODE_OK;
     if (B < 0 || T < 1 || !t || !ode_p || !nn_p || !nsteps || !status || !tape || !gy || !gx0) return HODE_EINVAL;
     if (!mode_ok(meal_mode, meal) || !mode_ok(tvns_mode, tvns) || !mode_ok(gd_mode, gd)) return HODE_EINVAL;
@@ -92,14 +94,24 @@ int solve_bwd(void *stream, int B, int T, const R *t, int t_batched, const R *me
     a.partials = (tuned_shape(H, L) || sizeof(R) == 4) ? (R *)((char *)tape + tape_partials_offset(B, max_steps, sizeof(R), H, L)) : nullptr;
     a.partial_rows = adj_partial_rows(B);
     a.act = act_of(L);
+    if (gmeal || gtvns || ggd) {
+        // input gradients: kernels of their own (include/hode.h); without them every call takes the path it took before
+        AdjInArgs<R> ai;
+        static_cast<AdjArgs<R> &>(ai) = a;
+        ai.gmeal = gmeal; ai.gtvns = gtvns; ai.ggd = ggd;
+        if (!tuned_shape(H, L)) return launch_solve_bwd_generic_gin<R>((hipStream_t)stream, ai, layers_of(L), method);
+        return launch_solve_bwd_inputs<R>((hipStream_t)stream, ai, layers_of(L), method);
+    }
     if (!tuned_shape(H, L)) return launch_solve_bwd_generic<R>((hipStream_t)stream, a, layers_of(L), method);
     return launch_solve_bwd<R>((hipStream_t)stream, a, layers_of(L), method);
 }
 
 template <typename R>
 int rhs_bwd(void *stream, int B, const R *x, const R *t, const R *meal, const R *tvns, const R *gd, const R *ode_p,
-            const R *nn_p, int H, int L, const R *gout, R *gx, R *gt, R *gnn, R *gode)
+            const R *nn_p, int H, int L, const R *gout, R *gx, R *gt, R *gnn, R *gode, R *gmeal = nullptr, R *gtvns = nullptr,
+            R *ggd = nullptr)
 {
+    if ((gmeal && !meal) || (gtvns && !tvns) || (ggd && !gd)) return HODE_EINVAL;
     if (B == 0) return HODE_OK;
     if (B < 0 || !x || !ode_p || !nn_p || !gout || !gx) return HODE_EINVAL;
     if (H < 1 || H > HODE_MAX_HIDDEN || layers_of(L) < 1 || layers_of(L) > HODE_MAX_LAYERS || act_of(L) > HODE_ACT_LEAKY_RELU || (L >> 16) != 0)
@@ -110,6 +122,7 @@ int rhs_bwd(void *stream, int B, const R *x, const R *t, const R *meal, const R 
     a.x = x; a.t = t; a.meal = meal; a.tvns = tvns; a.gd = gd; a.ode_p = ode_p; a.nn_p = nn_p;
     a.gout = gout; a.gx = gx; a.gt = gt; a.gnn = gnn; a.gode = gode;
     a.act = act_of(L);
+    a.gmeal = gmeal; a.gtvns = gtvns; a.ggd = ggd;
     if (!tuned_shape(H, L)) return launch_rhs_bwd_generic<R>((hipStream_t)stream, a, layers_of(L));
     return launch_rhs_bwd<R>((hipStream_t)stream, a, layers_of(L));
 }
@@ -187,6 +200,38 @@ int hode_solve_bwd_f64(void *stream, int B, int T, const double *t, int t_batche
 {
     return solve_bwd<double>(stream, B, T, t, t_batched, meal, meal_mode, tvns, tvns_mode, gd, gd_mode, ode_p, nn_p,
                              n_sets, H, L, method, max_steps, nsteps, status, tape, gy, gx0, gnn, gode);
+}
+
+int hode_rhs_bwd_inputs_f32(void *stream, int B, const float *x, const float *t, const float *meal, const float *tvns,
+                            const float *gd, const float *ode_p, const float *nn_p, int H, int L, const float *gout, float *gx,
+                            float *gt, float *gnn, float *gode, float *gmeal, float *gtvns, float *ggd)
+{
+    return rhs_bwd<float>(stream, B, x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, gx, gt, gnn, gode, gmeal, gtvns, ggd);
+}
+int hode_rhs_bwd_inputs_f64(void *stream, int B, const double *x, const double *t, const double *meal, const double *tvns,
+                            const double *gd, const double *ode_p, const double *nn_p, int H, int L, const double *gout,
+                            double *gx, double *gt, double *gnn, double *gode, double *gmeal, double *gtvns, double *ggd)
+{
+    return rhs_bwd<double>(stream, B, x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, gx, gt, gnn, gode, gmeal, gtvns, ggd);
+}
+
+int hode_solve_bwd_inputs_f32(void *stream, int B, int T, const float *t, int t_batched, const float *meal, int meal_mode,
+                              const float *tvns, int tvns_mode, const float *gd, int gd_mode, const float *ode_p,
+                              const float *nn_p, int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                              const int32_t *status, void *tape, const float *gy, float *gx0, float *gnn, float *gode,
+                              float *gmeal, float *gtvns, float *ggd)
+{
+    return solve_bwd<float>(stream, B, T, t, t_batched, meal, meal_mode, tvns, tvns_mode, gd, gd_mode, ode_p, nn_p,
+                            n_sets, H, L, method, max_steps, nsteps, status, tape, gy, gx0, gnn, gode, gmeal, gtvns, ggd);
+}
+int hode_solve_bwd_inputs_f64(void *stream, int B, int T, const double *t, int t_batched, const double *meal, int meal_mode,
+                              const double *tvns, int tvns_mode, const double *gd, int gd_mode, const double *ode_p,
+                              const double *nn_p, int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                              const int32_t *status, void *tape, const double *gy, double *gx0, double *gnn, double *gode,
+                              double *gmeal, double *gtvns, double *ggd)
+{
+    return solve_bwd<double>(stream, B, T, t, t_batched, meal, meal_mode, tvns, tvns_mode, gd, gd_mode, ode_p, nn_p,
+                             n_sets, H, L, method, max_steps, nsteps, status, tape, gy, gx0, gnn, gode, gmeal, gtvns, ggd);
 }
 
 int hode_adam_step_f32(void *stream, int64_t n, float *p, const float *g, float *m, float *v, float lr, float beta1,

@@ -1334,10 +1334,30 @@ __device__ __forceinline__ R mech_vjp(const OdeP<R> &o, R G, R I, R Glu, R GLP1,
 //   acts  h_1 .. h_NL of this evaluation.  (Recomputing h_1 here from (t, x, tvns) -- 9 FMAs instead of a 256-byte tape row
 //         per stage -- was built and measured: it costs the adjoint kernel its last registers, 80 B of scratch with
 //         reloads inside the stage loop, whose vmcnt waits serialise behind the record DMA: 8.1 -> 12.5 ms.)
-template <typename R, int NL, bool GODE, bool GT, typename Edge, typename Wt>
+// GIN: the cotangent kb pulled back to the three external inputs of one evaluation, in the input-gradient layout -- lanes 2q and
+// 2q + 1 receive input q (0 meal, 1 tVNS, 2 GD), every other lane GD's value (a wave-uniform select, no lane test for them):
+//   meal  enters dG additively (models/ode_core.py:148-150):  d f / d meal = lG;
+//   tVNS  enters the MLP only, as input 8 of the first layer:  ctv = sum_j W1[j][8] delta1_j  (the caller's wave_allsum);
+//   GD    enters k_GE = k_GE0 (1 - gde(GD)) only (:139-140):    lG k_GE0 G gde'(GD),  gde' = g u v / (GD (v + u)^2),
+//         u = GD^g, v = IGD_50^g; zero for GD <= 0 (the derivative the ODE-constant gradient of IGD_50 / g also takes there).
+template <typename R>
+__device__ __forceinline__ R input_vjp(const OdeP<R> &o, R G, R lG, R ctv, R gd_in, bool use_gd, int lane)
+{
+    R cg = R(0);
+    if (use_gd && gd_in > R(0)) {
+        const R u = rpow(gd_in, o.g), v = rpow(o.IGD_50, o.g);
+        cg = lG * o.k_GE0 * G * rdiv(o.g * u * v, gd_in * ((v + u) * (v + u)));
+    }
+    const int q = lane >> 1;
+    return (q == 0) ? lG : (q == 1) ? ctv : cg;
+}
+
+// GIN: *gin_out = input_vjp(...) of this evaluation (see above).
+template <typename R, int NL, bool GODE, bool GT, bool GIN = false, typename Edge, typename Wt>
 __device__ __forceinline__ R rhs_vjp(Edge &e, R (&gwh)[(NL > 1) ? NL - 1 : 1][kMaxH], const Wt &wt,
                                      const OdeP<R> &o, R t, R Y, R tvns, R gde, R gd_in, bool use_gd, int lane,
-                                     const MlpActs<R, NL> &acts, R kb, R &go, R *gt_out, const R *__restrict__ hrows = nullptr)
+                                     const MlpActs<R, NL> &acts, R kb, R &go, R *gt_out, const R *__restrict__ hrows = nullptr,
+                                     R *gin_out = nullptr)
 {
     // hrows: LDS copy of the record rows h_1 .. h_NL ([NL][64]) or nullptr
     using S = EdgeSlots<NL>;
@@ -1399,6 +1419,7 @@ __device__ __forceinline__ R rhs_vjp(Edge &e, R (&gwh)[(NL > 1) ? NL - 1 : 1][kM
     p[5] = w16 * d;
     const R nn = wave_reduce6_to_lanes(p, lane);
     if constexpr (GT) *gt_out = wave_allsum(e.W(S::w1 + 0) * d);
+    if constexpr (GIN) *gin_out = input_vjp(o, G, lG, wave_allsum(e.W(S::w1 + 8) * d), gd_in, use_gd, lane);
     return (c8 < 6) ? (mech + nn) : R(0);
 }
 

@@ -21,6 +21,10 @@
 #include "hode_solve_body.h"
 #include <type_traits>
 
+// HODE_GENERIC_GIN: this file compiled a second time by hode_generic_gin.hip.  The #ifdef HODE_GENERIC_GIN blocks below add the input
+// gradients (d/d meal, tVNS, GD; include/hode.h) to the one-trajectory adjoint and to the RHS backward, and the two kernels carry other
+// names there.  Compiled on its own (libhode's production kernels) the file is exactly the code without them.
+
 namespace hode {
 
 // one parameter set in the flat PyTorch parameters() layout (include/hode.h)
@@ -572,7 +576,11 @@ template <int RPW> struct IsTeamAcc<TeamAccT<RPW>> { static constexpr bool v = t
 template <typename R, bool GODE, bool GT, int NW = 1, typename ACC = NoAcc, typename EW = EdgeFromParams<R>>
 __device__ __forceinline__ R rhs_vjp_stream(const StreamNet<R> &n, const EW &ew, R *__restrict__ g, const OdeP<R> &o, R t, R tvns, R gde, R gd_in,
                                             bool use_gd, int lane, const R *__restrict__ rec, R kb, R &go, R *gt_out, int part,
-                                            R *__restrict__ xch, ACC &acc, int &xpar)
+                                            R *__restrict__ xch, ACC &acc, int &xpar
+#ifdef HODE_GENERIC_GIN
+                                            , R *gin_out             // the input cotangents of this evaluation (input_vjp, hode_device.h)
+#endif
+                                            )
 {
     const int H = n.H, L = n.L;
     const R *__restrict__ sx = rec + 2 * L * kWave;            // the stage state: wave-uniform loads
@@ -760,6 +768,9 @@ __device__ __forceinline__ R rhs_vjp_stream(const StreamNet<R> &n, const EW &ew,
     const R p[6] = {w[1], w[2], w[3], w[4] + w[7], w[5], w[6]};                                   // GLP1 feeds inputs 4 and 7
     const R nn = wave_reduce6_to_lanes(p, lane);
     if constexpr (GT) *gt_out = wave_allsum(w[0]);
+#ifdef HODE_GENERIC_GIN
+    *gin_out = input_vjp(o, G, lq[0], wave_allsum(w[8]), gd_in, use_gd, lane);
+#endif
     return (c8 < 6) ? (mech + nn) : R(0);
 }
 
@@ -801,10 +812,23 @@ __global__ __launch_bounds__(256) void rhs_bwd_generic_kernel(const RhsArgs<R> a
         R gt;
         NoAcc na;
         int xpar = 0;                                            // (one wave per sample: no exchange)
+#ifndef HODE_GENERIC_GIN
         const R Z = rhs_vjp_stream<R, GODE, true>(n, EdgeFromParams<R>{n}, a.gnn, o, t, tvns, gde, gdv, a.gd != nullptr, lane, rec, kb, go, &gt, 0, (R *)nullptr, na, xpar);
+#else
+        R cin;
+        const R Z = rhs_vjp_stream<R, GODE, true>(n, EdgeFromParams<R>{n}, a.gnn, o, t, tvns, gde, gdv, a.gd != nullptr, lane, rec, kb, go, &gt, 0, (R *)nullptr, na, xpar,
+                                                  &cin);
+#endif
         __builtin_amdgcn_wave_barrier();
         if (lane < 6) a.gx[(size_t)s * 6 + lane] = Z;
         if (a.gt && lane == 0) a.gt[s] = gt;
+#ifdef HODE_GENERIC_GIN
+        {
+            // lane 2q holds input q's cotangent (input_vjp)
+            R *__restrict__ gq = (lane == 0) ? a.gmeal : (lane == 2) ? a.gtvns : (lane == 4) ? a.ggd : nullptr;
+            if (gq) gq[s] = cin;
+        }
+#endif
     }
     if constexpr (GODE) {
         if (a.gode && lane < 17) atomic_add(a.gode + lane, go);
@@ -821,6 +845,9 @@ template <typename R> int launch_rhs_fwd_generic(hipStream_t s, const RhsArgs<R>
 }
 template <typename R> int launch_rhs_bwd_generic(hipStream_t s, const RhsArgs<R> &a, int L)
 {
+#ifndef HODE_GENERIC_GIN
+    if (a.gmeal || a.gtvns || a.ggd) return launch_rhs_bwd_generic_gin<R>(s, a, L);      // (hode_generic_gin.hip)
+#endif
     int blocks = (a.B + 3) / 4;
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) return HODE_OK;
@@ -969,7 +996,11 @@ template <typename R> int launch_solve_fwd_generic(hipStream_t s, const SolveArg
 // register accumulators (TeamAccT), else gradients leave through atomics inside rhs_vjp_stream (fp64, more than four hidden
 // matrices, no parameter gradient wanted).
 template <typename R, bool GODE, bool GD, int kGenTeam, int ACCREG>      // ACCREG: accumulator rows per wave (8 / 16), 0 = atomics
+#ifndef HODE_GENERIC_GIN
 __global__ __launch_bounds__(64 * kGenTeam) void solve_bwd_generic_kernel(const AdjArgs<R> a, const int method, const int L, const int rows_grid)
+#else
+__global__ __launch_bounds__(64 * kGenTeam) void solve_bwd_generic_kernel(const AdjInArgs<R> a, const int method, const int L, const int rows_grid)
+#endif
 {
     using Acc = std::conditional_t<ACCREG != 0, TeamAccT<ACCREG ? ACCREG : 8>, NoAcc>;
     Acc acc;
@@ -1036,9 +1067,33 @@ __global__ __launch_bounds__(64 * kGenTeam) void solve_bwd_generic_kernel(const 
         auto gy_row = [&](int r) -> R { return (c8 < 6) ? gyb[(size_t)r * 6 + c8] : R(0); };
         R lam = R(0), go = R(0);
         int knext = T - 1;
+#ifdef HODE_GENERIC_GIN
+        // input gradients: the one-register layout and the walk of solve_bwd_kernel (hode_solve_bwd.hip); the team's first wave writes
+        R gin = R(0);
+        int kin = T, whi = T - 1;
+        auto gin_flush = [&](int knew) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                R *__restrict__ gq = (q == 0) ? a.gmeal : (q == 1) ? a.gtvns : a.ggd;
+                const int mq = (q == 0) ? a.meal_mode : (q == 1) ? a.tvns_mode : a.gd_mode;
+                if (gq == nullptr || mq != 2) continue;
+                const R lo = lane_bcast(gin, 2 * q), up = lane_bcast(gin, 2 * q + 1);
+                for (int r = knew + 2; r <= whi; ++r)
+                    if (part == 0 && lane == 0) gq[(size_t)b * T + r] = (r == kin + 1) ? up : (r == kin) ? lo : R(0);
+            }
+            const bool row2 = ((lane >> 1) == 0) ? a.meal_mode == 2 : ((lane >> 1) == 1) ? a.tvns_mode == 2 : a.gd_mode == 2;
+            const R nb = xlane_xor1(gin);
+            gin = row2 ? (((lane & 1) && kin == knew + 1) ? nb : R(0)) : gin;
+            kin = knew;
+            whi = knew + 1;
+        };
+#endif
         for (int st = nst - 1; st >= 0; --st) {
             const int kraw = tseg[st];
             const int k = kraw & (kSegClosed - 1);
+#ifdef HODE_GENERIC_GIN
+            if (k != kin) gin_flush(k);
+#endif
             int hi = knext;                                   // rows this step produced: see solve_bwd_kernel
             if (st == nst - 1) {
                 hi = T - 1;
@@ -1067,8 +1122,19 @@ __global__ __launch_bounds__(64 * kGenTeam) void solve_bwd_generic_kernel(const 
                 const R gdv = rfma(al, dd, d0);
                 R gde = R(0);
                 if constexpr (use_gd) gde = gd_effect(o, gdv);
+#ifndef HODE_GENERIC_GIN
                 const R Z = rhs_vjp_stream<R, GODE, false, kGenTeam, Acc, EdgeImage<R>>(n, ew, g, o, ts, rfma(al, dv, v0), gde, gdv, use_gd, lane,
                                                                           stg + ((size_t)st * 6 + s) * kSlot, kb, go, nullptr, part, xch, acc, xpar);
+#else
+                R cin;
+                const R Z = rhs_vjp_stream<R, GODE, false, kGenTeam, Acc, EdgeImage<R>>(n, ew, g, o, ts, rfma(al, dv, v0), gde, gdv, use_gd, lane,
+                                                                          stg + ((size_t)st * 6 + s) * kSlot, kb, go, nullptr, part, xch, acc, xpar, &cin);
+                {
+                    const int mq = ((lane >> 1) == 0) ? a.meal_mode : ((lane >> 1) == 1) ? a.tvns_mode : a.gd_mode;
+                    const R w = (mq == 2) ? ((lane & 1) ? al : R(1) - al) : (mq == 1 && !(lane & 1)) ? R(1) : R(0);
+                    gin = rfma(w, cin, gin);
+                }
+#endif
                 ZZ = (grp == s) ? Z : ZZ;
             }
             lam += group_sum8(rowsT[7 * kWave + lane] * ZZ);
@@ -1076,6 +1142,16 @@ __global__ __launch_bounds__(64 * kGenTeam) void solve_bwd_generic_kernel(const 
         int kf = 0;                                           // rows 0..kf are (copies of) x0
         while (kf + 1 < T && !(tg[kf + 1] > tg[kf])) ++kf;
         for (int r = 0; r <= kf; ++r) lam += gy_row(r);
+#ifdef HODE_GENERIC_GIN
+        gin_flush(-2);                                        // rows 0 .. whi
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            R *__restrict__ gq = (q == 0) ? a.gmeal : (q == 1) ? a.gtvns : a.ggd;
+            const int mq = (q == 0) ? a.meal_mode : (q == 1) ? a.tvns_mode : a.gd_mode;
+            const R v = lane_bcast(gin, 2 * q);
+            if (gq != nullptr && mq == 1 && part == 0 && lane == 0) gq[b] = v;
+        }
+#endif
         if (part == 0) {
             if (lane < 6) a.gx0[(size_t)b * 6 + lane] = lam;
             if constexpr (GODE) {
@@ -1511,7 +1587,11 @@ template <int TB, int RPW> static int launch_bwd_generic_multi(hipStream_t s, co
     return hipGetLastError() == hipSuccess ? HODE_OK : HODE_ELAUNCH;
 }
 
+#ifndef HODE_GENERIC_GIN
 template <typename R, int NW, int ACCREG> static int launch_bwd_generic_t(hipStream_t s, const AdjArgs<R> &a, int L, int method)
+#else
+template <typename R, int NW, int ACCREG> static int launch_bwd_generic_t(hipStream_t s, const AdjInArgs<R> &a, int L, int method)
+#endif
 {
     // with register accumulators a workgroup flushes once: fewer, longer-lived workgroups (a few per CU) beat one per trajectory
     int blocks = a.B < 4096 ? a.B : 4096;
@@ -1545,6 +1625,18 @@ template <typename R, int NW, int ACCREG> static int launch_bwd_generic_t(hipStr
     }
     return hipGetLastError() == hipSuccess ? HODE_OK : HODE_ELAUNCH;
 }
+#ifdef HODE_GENERIC_GIN
+// input gradients: the one-trajectory teams for every batch (register accumulators where the production path has them, atomics
+// elsewhere -- the same families as launch_solve_bwd_generic below, without the multi-trajectory teams)
+template <typename R> int launch_solve_bwd_generic_gin(hipStream_t s, const AdjInArgs<R> &a, int L, int method)
+{
+    if constexpr (sizeof(R) == 4) {
+        if (L - 1 <= kGenAccMats && a.gnn != nullptr)
+            return a.H > 64 ? launch_bwd_generic_t<R, 8, 16>(s, a, L, method) : launch_bwd_generic_t<R, 8, 8>(s, a, L, method);
+    }
+    return a.H > 64 ? launch_bwd_generic_t<R, 16, 0>(s, a, L, method) : launch_bwd_generic_t<R, 8, 0>(s, a, L, method);
+}
+#else
 template <typename R> int launch_solve_bwd_generic(hipStream_t s, const AdjArgs<R> &a, int L, int method)
 {
     if constexpr (sizeof(R) == 4) {
@@ -1571,6 +1663,14 @@ template <typename R> int launch_solve_bwd_generic(hipStream_t s, const AdjArgs<
     return a.H > 64 ? launch_bwd_generic_t<R, 16, 0>(s, a, L, method) : launch_bwd_generic_t<R, 8, 0>(s, a, L, method);
 }
 
+#endif
+
+#ifdef HODE_GENERIC_GIN
+template int launch_rhs_bwd_generic_gin<float>(hipStream_t, const RhsArgs<float> &, int);
+template int launch_rhs_bwd_generic_gin<double>(hipStream_t, const RhsArgs<double> &, int);
+template int launch_solve_bwd_generic_gin<float>(hipStream_t, const AdjInArgs<float> &, int, int);
+template int launch_solve_bwd_generic_gin<double>(hipStream_t, const AdjInArgs<double> &, int, int);
+#else
 template int launch_rhs_fwd_generic<float>(hipStream_t, const RhsArgs<float> &, int);
 template int launch_rhs_fwd_generic<double>(hipStream_t, const RhsArgs<double> &, int);
 template int launch_rhs_bwd_generic<float>(hipStream_t, const RhsArgs<float> &, int);
@@ -1579,5 +1679,6 @@ template int launch_solve_fwd_generic<float>(hipStream_t, const SolveArgs<float>
 template int launch_solve_fwd_generic<double>(hipStream_t, const SolveArgs<double> &, int);
 template int launch_solve_bwd_generic<float>(hipStream_t, const AdjArgs<float> &, int, int);
 template int launch_solve_bwd_generic<double>(hipStream_t, const AdjArgs<double> &, int, int);
+#endif
 
 }  // namespace hode

@@ -34,6 +34,11 @@ template <typename R> struct AdjArgs {
     int partial_rows;
     int act;            // HODE_ACT_* (generic kernels)
 };
+// AdjArgs + the input gradients (hode_solve_bwd_inputs_*): NULL, or [B] / [B,T] by the input's mode (1 / 2); WRITTEN, not
+// accumulated.  Only the input-gradient kernels take it: every other adjoint kernel keeps its AdjArgs argument block.
+template <typename R> struct AdjInArgs : AdjArgs<R> {
+    R *gmeal, *gtvns, *ggd;
+};
 
 template <typename R> struct RhsArgs {
     int B, H, P;
@@ -42,6 +47,7 @@ template <typename R> struct RhsArgs {
     const R *gout;          // bwd
     R *gx, *gt, *gnn, *gode;
     int act;                // HODE_ACT_* (generic kernels)
+    R *gmeal, *gtvns, *ggd; // bwd, input gradients [B] (hode_rhs_bwd_inputs_*): written; NULL = not wanted
 };
 
 template <typename R> int launch_solve_fwd(hipStream_t s, const SolveArgs<R> &a, int L, int method);
@@ -53,6 +59,8 @@ int launch_solve_fwd_quad(hipStream_t s, const SolveArgs<float> &a, int L, int m
 int launch_solve_fwd_rows(hipStream_t s, const SolveArgs<float> &a, int L, int method); // lab/hode_solve_fwd_rows.hip (fp32, L = 2..4)
 #endif
 template <typename R> int launch_solve_bwd(hipStream_t s, const AdjArgs<R> &a, int L, int method);
+// the same with input gradients (solve_bwd_kernel, GIN instantiations; tuned shapes, every dtype)
+template <typename R> int launch_solve_bwd_inputs(hipStream_t s, const AdjInArgs<R> &a, int L, int method);
 // wave-specialised fp32 adjoint (hode_solve_bwd_ws.hip; L = 2..4, needs the partial rows); HODE_EUNSUPPORTED -> solve_bwd_kernel
 int launch_solve_bwd_ws(hipStream_t s, const AdjArgs<float> &a, int L, int method, int cus);
 // second pass of the gradient reduction: rows of a.partials added in workgroup order (hode_solve_bwd.hip)
@@ -64,6 +72,9 @@ template <typename R> int launch_solve_fwd_generic(hipStream_t s, const SolveArg
 template <typename R> int launch_solve_bwd_generic(hipStream_t s, const AdjArgs<R> &a, int L, int method);
 template <typename R> int launch_rhs_fwd_generic(hipStream_t s, const RhsArgs<R> &a, int L);
 template <typename R> int launch_rhs_bwd_generic(hipStream_t s, const RhsArgs<R> &a, int L);
+// the same with input gradients (hode_generic_gin.hip; launch_*_generic route requests there): one-trajectory teams for every batch
+template <typename R> int launch_solve_bwd_generic_gin(hipStream_t s, const AdjInArgs<R> &a, int L, int method);
+template <typename R> int launch_rhs_bwd_generic_gin(hipStream_t s, const RhsArgs<R> &a, int L);
 // shapes the tuned (register-resident) kernels are compiled for; everything else up to HODE_MAX_* takes the generic path
 // The `L` argument of the C ABI carries the number of hidden layers in bits 0..7 and the activation (HODE_ACT_*) in bits 8..15.
 inline int layers_of(int L) { return L & 0xff; }

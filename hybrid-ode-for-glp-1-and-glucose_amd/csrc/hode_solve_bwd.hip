@@ -62,8 +62,13 @@ template <typename R, int NL> __host__ __device__ constexpr size_t bwd_lds_elems
 // WTREG = false: kBwdWaves (8) waves per workgroup, transposed matrices in LDS, 2 waves/SIMD.
 // WTREG = true (fp32): 4 waves per workgroup, transposed matrices in registers, 1 wave/SIMD, no LDS wait
 //         inside the 64-FMA loops.
-template <typename R, int NL, bool GODE, bool WTREG, bool GD>
-__global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !WTREG ? 2 : 1)) void solve_bwd_kernel(const AdjArgs<R> a, const int method)
+// GIN: also the gradients of the external inputs (a.gmeal / a.gtvns / a.ggd), see gin_flush below.
+// (the GIN instantiations take AdjInArgs: the argument block of the others stays AdjArgs)
+template <typename R> __device__ __forceinline__ R *gin_row(const AdjArgs<R> &, int) { return nullptr; }
+template <typename R> __device__ __forceinline__ R *gin_row(const AdjInArgs<R> &a, int q) { return (q == 0) ? a.gmeal : (q == 1) ? a.gtvns : a.ggd; }
+template <typename R, bool GIN> using AdjArgsT = std::conditional_t<GIN, AdjInArgs<R>, AdjArgs<R>>;
+template <typename R, int NL, bool GODE, bool WTREG, bool GD, bool GIN>
+__global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !WTREG ? 2 : 1)) void solve_bwd_kernel(const AdjArgsT<R, GIN> a, const int method)
 {
     constexpr int kWaves = WTREG ? 4 : kBwdWaves;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -155,6 +160,30 @@ __global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !W
         const bool ok = a.status[b] == HODE_ST_OK;
         R lam = R(0);                              // cotangent of the state, replicated per 8-lane group
         int knext = T - 1;                         // grid interval of the step after the current one
+        // GIN: input gradients in ONE register.  Input q (0 meal, 1 tVNS, 2 GD) has the stage value u_s = u_k + al_s (u_{k+1} - u_k)
+        // on interval k, so a stage's input cotangent c_s (input_vjp) adds (1 - al_s) c_s to grid row k and al_s c_s to row k + 1:
+        // lane 2q holds input q's sum for row kin, lane 2q + 1 for row kin + 1 (mode 1: lane 2q the whole sum, weight 1).  The reverse
+        // walk meets the intervals in decreasing order; when it leaves interval kin for knew every row above knew + 1 is final and is
+        // WRITTEN (rows no taped step touches -- after a failure, inside a run of repeated grid times -- are written 0), and row kin
+        // moves to the row-(knew + 1) lane if it is shared with the new interval.  One trajectory per wave: no atomics.
+        R gin = R(0);
+        int kin = T, whi = T - 1;                  // interval of the sums in gin (T: none yet); rows above whi are written
+        auto gin_flush = [&](int knew) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                R *__restrict__ gq = gin_row(a, q);
+                const int mq = (q == 0) ? a.meal_mode : (q == 1) ? a.tvns_mode : a.gd_mode;
+                if (gq == nullptr || mq != 2) continue;
+                const R lo = lane_bcast(gin, 2 * q), up = lane_bcast(gin, 2 * q + 1);
+                for (int r = knew + 2; r <= whi; ++r)
+                    if (lane == 0) gq[(size_t)b * T + r] = (r == kin + 1) ? up : (r == kin) ? lo : R(0);
+            }
+            const bool row2 = ((lane >> 1) == 0) ? a.meal_mode == 2 : ((lane >> 1) == 1) ? a.tvns_mode == 2 : a.gd_mode == 2;
+            const R nb = xlane_xor1(gin);                                          // odd lanes: row kin of the same input
+            gin = row2 ? (((lane & 1) && kin == knew + 1) ? nb : R(0)) : gin;      // (mode-1 sums stay)
+            kin = knew;
+            whi = knew + 1;
+        };
         // Stage records stream HBM -> LDS by DMA (no VGPR destination): while stage s is processed from one
         // half of the wave's double buffer, the record of the next stage (also across step boundaries) lands
         // in the other half.
@@ -175,6 +204,9 @@ __global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !W
         for (int st = n - 1; st >= 0; --st) {
             const int kraw = tseg[st];
             const int k = kraw & (kSegClosed - 1);
+            if constexpr (GIN) {
+                if (k != kin) gin_flush(k);
+            }
             // cotangents of the grid rows this step produced (row k+1 and any repeated rows that follow it).  The last step
             // of a FAILED trajectory: if it closed its interval, row k+1 and the copies behind it (zero-length intervals up
             // to the interval that failed) were still written; if it did not, nothing after row k was.
@@ -235,9 +267,15 @@ __global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !W
                 const R gdv = rfma(al, dd, d0);
                 R gde = R(0);
                 if constexpr (use_gd) gde = gd_effect(o, gdv);
-                const R Z = rhs_vjp<R, NL, GODE, false>(E, gwh, wtp, o, ts, Ys, rfma(al, dv, v0), gde, gdv, use_gd, lane, ac, kb,
-                                                        go, nullptr, hrows);
+                R cin = R(0);
+                const R Z = rhs_vjp<R, NL, GODE, false, GIN>(E, gwh, wtp, o, ts, Ys, rfma(al, dv, v0), gde, gdv, use_gd, lane, ac, kb,
+                                                             go, nullptr, hrows, &cin);
                 ZZ = (grp == s) ? Z : ZZ;
+                if constexpr (GIN) {
+                    const int mq = ((lane >> 1) == 0) ? a.meal_mode : ((lane >> 1) == 1) ? a.tvns_mode : a.gd_mode;
+                    const R w = (mq == 2) ? ((lane & 1) ? al : R(1) - al) : (mq == 1 && !(lane & 1)) ? R(1) : R(0);
+                    gin = rfma(w, cin, gin);
+                }
             }
             lam += group_sum8(rowsT[7 * kWave + lane] * ZZ);
         }
@@ -252,6 +290,16 @@ __global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !W
             lam += (c8 == 0) ? g0 : (c8 == 1) ? g1 : (c8 == 2) ? g2 : (c8 == 3) ? g3 : (c8 == 4) ? g4 : (c8 == 5) ? g5 : R(0);
         }
         if (lane < 6) a.gx0[(size_t)b * 6 + lane] = lam;
+        if constexpr (GIN) {
+            gin_flush(-2);                                                         // rows 0 .. whi
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                R *__restrict__ gq = gin_row(a, q);
+                const int mq = (q == 0) ? a.meal_mode : (q == 1) ? a.tvns_mode : a.gd_mode;
+                const R v = lane_bcast(gin, 2 * q);
+                if (gq != nullptr && mq == 1 && lane == 0) gq[b] = v;
+            }
+        }
     }
 
     // ---- epilogue: ONE gradient row per workgroup, no floating-point atomics ------------------------------------------------
@@ -386,7 +434,7 @@ static int device_cu_count()
     return cached[dev];
 }
 
-template <typename R, int NL, bool GODE, bool WTREG, bool GD> static int launch_bwd_g(hipStream_t s, const AdjArgs<R> &a, int method)
+template <typename R, int NL, bool GODE, bool WTREG, bool GD, bool GIN> static int launch_bwd_g(hipStream_t s, const AdjArgs<R> &a, int method)
 {
     constexpr int kW = WTREG ? 4 : kBwdWaves;
     const int per_set = a.B / a.n_sets;
@@ -398,10 +446,10 @@ template <typename R, int NL, bool GODE, bool WTREG, bool GD> static int launch_
     if (blocks < 1) blocks = 1;
     const size_t lds = bwd_lds_elems<R, NL>() * sizeof(R);
     dim3 grid(blocks, a.n_sets), block(64 * kW);
-    auto kern = solve_bwd_kernel<R, NL, GODE, WTREG, GD>;
+    auto kern = solve_bwd_kernel<R, NL, GODE, WTREG, GD, GIN>;
     if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return HODE_ELAUNCH;
-    AdjArgs<R> a2 = a;
+    AdjArgsT<R, GIN> a2 = static_cast<const AdjArgsT<R, GIN> &>(a);      // (GIN: the caller passed an AdjInArgs)
     if (blocks * a.n_sets > a.partial_rows) a2.partials = nullptr;       // more parameter sets than rows: atomics
     hipLaunchKernelGGL(kern, grid, block, lds, s, a2, method);
     if (a2.partials && (a.gnn || (GODE && a.gode))) {
@@ -412,9 +460,9 @@ template <typename R, int NL, bool GODE, bool WTREG, bool GD> static int launch_
     return hipGetLastError() == hipSuccess ? HODE_OK : HODE_ELAUNCH;
 }
 
-template <typename R, int NL, bool GODE, bool WTREG> static int launch_bwd_k(hipStream_t s, const AdjArgs<R> &a, int method)
+template <typename R, int NL, bool GODE, bool WTREG, bool GIN = false> static int launch_bwd_k(hipStream_t s, const AdjArgs<R> &a, int method)
 {
-    return a.gd_mode != 0 ? launch_bwd_g<R, NL, GODE, WTREG, true>(s, a, method) : launch_bwd_g<R, NL, GODE, WTREG, false>(s, a, method);
+    return a.gd_mode != 0 ? launch_bwd_g<R, NL, GODE, WTREG, true, GIN>(s, a, method) : launch_bwd_g<R, NL, GODE, WTREG, false, GIN>(s, a, method);
 }
 
 #ifdef HODE_LAB
@@ -480,10 +528,29 @@ template <typename R> int launch_solve_bwd(hipStream_t s, const AdjArgs<R> &a, i
 template int launch_solve_bwd<float>(hipStream_t, const AdjArgs<float> &, int, int);
 template int launch_solve_bwd<double>(hipStream_t, const AdjArgs<double> &, int, int);
 
+// input gradients: the GIN instantiations of the one-role kernel (transposed matrices in LDS) for every tuned shape and dtype -- the
+// wave-specialised fp32 kernel has none
+template <typename R> int launch_solve_bwd_inputs(hipStream_t s, const AdjInArgs<R> &a, int L, int method)
+{
+    auto nl = [&](auto NLc) {
+        constexpr int NL = decltype(NLc)::value;
+        return a.gode ? launch_bwd_k<R, NL, true, false, true>(s, a, method) : launch_bwd_k<R, NL, false, false, true>(s, a, method);
+    };
+    switch (L) {
+    case 1: return nl(std::integral_constant<int, 1>{});
+    case 2: return nl(std::integral_constant<int, 2>{});
+    case 3: return nl(std::integral_constant<int, 3>{});
+    case 4: return nl(std::integral_constant<int, 4>{});
+    }
+    return HODE_EUNSUPPORTED;
+}
+template int launch_solve_bwd_inputs<float>(hipStream_t, const AdjInArgs<float> &, int, int);
+template int launch_solve_bwd_inputs<double>(hipStream_t, const AdjInArgs<double> &, int, int);
+
 // ------------------------------------------------------------------------------------------
 // K5: RHS backward.  Replaces torch autograd over ode_residual in the physics loss
-// (reference models/hybrid_ode_nn.py:318-330).  Same mapping; one sample per wave.
-template <typename R, int NL, bool GODE>
+// (reference models/hybrid_ode_nn.py:318-330).  Same mapping; one sample per wave.  GIN: also d/d(meal, tVNS, GD) per sample.
+template <typename R, int NL, bool GODE, bool GIN>
 __global__ __launch_bounds__(256, 1) void rhs_bwd_kernel(const RhsArgs<R> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -521,10 +588,16 @@ __global__ __launch_bounds__(256, 1) void rhs_bwd_kernel(const RhsArgs<R> a)
         const R gde = a.gd ? gd_effect(o, gdv) : R(0);
         MlpActs<R, NL> ac;
         (void)rhs_eval<R, NL, true>(W, o, t, Y, meal, tvns, gde, lane, &ac);
-        R gt;
-        const R Z = rhs_vjp<R, NL, GODE, true>(E, gwh, WtLds<R>{wt}, o, t, Y, tvns, gde, gdv, a.gd != nullptr, lane, ac, kb, go, &gt);
+        R gt, cin = R(0);
+        const R Z = rhs_vjp<R, NL, GODE, true, GIN>(E, gwh, WtLds<R>{wt}, o, t, Y, tvns, gde, gdv, a.gd != nullptr, lane, ac, kb, go, &gt,
+                                                    nullptr, &cin);
         if (lane < 6) a.gx[(size_t)s * 6 + lane] = Z;
         if (a.gt && lane == 0) a.gt[s] = gt;
+        if constexpr (GIN) {
+            // lane 2q holds input q's cotangent (input_vjp)
+            R *__restrict__ gq = (lane == 0) ? a.gmeal : (lane == 2) ? a.gtvns : (lane == 4) ? a.ggd : nullptr;
+            if (gq) gq[s] = cin;
+        }
     }
     // ---- the four waves' accumulators are summed in LDS first (the image of the transposed matrices is dead now) and ONE wave
     //      flushes: the flush is P atomics per wave on the same 54 KB, and it -- not the arithmetic -- is what the kernel costs.  Round
@@ -578,17 +651,12 @@ template <typename R, int NL> static int launch_rhs_bwd_nl(hipStream_t s, const 
         const size_t red = ((size_t)(NL > 1 ? NL - 1 : 0) * kMaxH + EdgeSlots<NL>::count + 1) * kWave * sizeof(R);   // the workgroup reduction
         if (lds < red) lds = red;
     }
-    if (a.gode) {
-        auto kern = rhs_bwd_kernel<R, NL, true>;
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return HODE_ELAUNCH;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, a);
-    } else {
-        auto kern = rhs_bwd_kernel<R, NL, false>;
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return HODE_ELAUNCH;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, a);
-    }
+    const bool gin = a.gmeal || a.gtvns || a.ggd;
+    auto kern = a.gode ? (gin ? rhs_bwd_kernel<R, NL, true, true> : rhs_bwd_kernel<R, NL, true, false>)
+                       : (gin ? rhs_bwd_kernel<R, NL, false, true> : rhs_bwd_kernel<R, NL, false, false>);
+    if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return HODE_ELAUNCH;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, a);
     return hipGetLastError() == hipSuccess ? HODE_OK : HODE_ELAUNCH;
 }
 

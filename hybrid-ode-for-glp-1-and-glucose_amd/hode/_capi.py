@@ -21,7 +21,10 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_rhs_bwd_f32", "hode_rhs_bwd_f64", "hode_solve_fwd_f32", "hode_solve_fwd_f64",
            "hode_solve_bwd_f32", "hode_solve_bwd_f64", "hode_adam_step_f32", "hode_mse_fwd_bwd_f32",
            "hode_selftest_xlane", "hode_4gi_default_params", "hode_4gi_generate_f64", "hode_4gi_rhs_f64",
-           "hode_4gi_windows_f32", "hode_4gi_window_moments_f64"]
+           "hode_4gi_windows_f32", "hode_4gi_window_moments_f64",
+           "hode_solve_bwd_inputs_f32", "hode_solve_bwd_inputs_f64", "hode_rhs_bwd_inputs_f32", "hode_rhs_bwd_inputs_f64"]
+
+INPUT_KEYS = ("meal", "tVNS", "GD")
 
 
 class HodeError(RuntimeError):
@@ -213,6 +216,17 @@ def solve_fwd(x0, t, meal, tvns, gd, ode_p, nn_p, H, L, method=METHOD_DP54, rtol
 def solve_bwd(sol, gy, want_gnn=True, want_gode=False):
     """Reverse-time discrete adjoint over the tape of `sol` (made with want_tape=True).
     Returns (gx0[B,6], gnn[n_sets*P] or None, gode[n_sets*17] or None)."""
+    return _solve_bwd(sol, gy, want_gnn, want_gode, None)[:3]
+
+
+def solve_bwd_inputs(sol, gy, want_gnn=True, want_gode=False, want_inputs=INPUT_KEYS):
+    """solve_bwd() + the gradients of the external inputs (hode_solve_bwd_inputs_*, include/hode.h).
+    Returns (gx0, gnn, gode, {"meal", "tVNS", "GD"}): an entry is None for an input the solve did not have or that is not in
+    `want_inputs`, else a tensor shaped like the input ([B] constant, [B,T] on the grid)."""
+    return _solve_bwd(sol, gy, want_gnn, want_gode, tuple(want_inputs))
+
+
+def _solve_bwd(sol, gy, want_gnn, want_gode, want_inputs):
     if sol.tape is None:
         raise HodeError("solve_bwd needs a solution computed with want_tape=True")
     t, t_batched, meal, tvns, gd, ode_p, nn_p, n_sets, H, L, method = sol.ctx
@@ -224,17 +238,33 @@ def solve_bwd(sol, gy, want_gnn=True, want_gode=False):
     gx0 = torch.empty(B, 6, dtype=dt, device=dev)
     gnn = torch.zeros(nn_p.numel(), dtype=dt, device=dev) if want_gnn else None
     gode = torch.zeros(17 * n_sets, dtype=dt, device=dev) if want_gode else None
-    fn = getattr(load(), f"hode_solve_bwd_{_sfx(dt)}")
-    rc = fn(_stream(), C.c_int(B), C.c_int(T), _ptr(t), C.c_int(t_batched),
+    args = [_stream(), C.c_int(B), C.c_int(T), _ptr(t), C.c_int(t_batched),
             _ptr(meal), C.c_int(_mode(meal, B, T)), _ptr(tvns), C.c_int(_mode(tvns, B, T)),
             _ptr(gd), C.c_int(_mode(gd, B, T)), _ptr(ode_p), _ptr(nn_p), C.c_int(n_sets), C.c_int(H), C.c_int(L),
             C.c_int(method), C.c_int(sol.max_steps), _ptr(sol.nsteps), _ptr(sol.status), _ptr(sol.tape), _ptr(gy),
-            _ptr(gx0), _ptr(gnn), _ptr(gode))
-    _check(rc, "hode_solve_bwd")
-    return gx0, gnn, gode
+            _ptr(gx0), _ptr(gnn), _ptr(gode)]
+    if want_inputs is None:
+        _check(getattr(load(), f"hode_solve_bwd_{_sfx(dt)}")(*args), "hode_solve_bwd")
+        return gx0, gnn, gode, None
+    gin = {k: (torch.empty_like(u) if (u is not None and k in want_inputs) else None)
+           for k, u in zip(INPUT_KEYS, (meal, tvns, gd))}
+    _check(getattr(load(), f"hode_solve_bwd_inputs_{_sfx(dt)}")(*args, *(_ptr(gin[k]) for k in INPUT_KEYS)),
+           "hode_solve_bwd_inputs")
+    return gx0, gnn, gode, gin
 
 
 def rhs_bwd(x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, want_gt=False, want_gnn=True, want_gode=False):
+    return _rhs_bwd(x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, want_gt, want_gnn, want_gode, None)[:4]
+
+
+def rhs_bwd_inputs(x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, want_gt=False, want_gnn=True, want_gode=False,
+                   want_inputs=INPUT_KEYS):
+    """rhs_bwd() + the gradients of the external inputs (hode_rhs_bwd_inputs_*): returns (gx, gt, gnn, gode,
+    {"meal", "tVNS", "GD"}), an entry [B] for an input that is given and wanted, else None."""
+    return _rhs_bwd(x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, want_gt, want_gnn, want_gode, tuple(want_inputs))
+
+
+def _rhs_bwd(x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, want_gt, want_gnn, want_gode, want_inputs):
     _need_gpu(x)
     dt, dev = x.dtype, x.device
     x = x.contiguous()
@@ -245,10 +275,15 @@ def rhs_bwd(x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, want_gt=False, want_g
     gt = torch.empty(B, dtype=dt, device=dev) if want_gt else None
     gnn = torch.zeros(nn_p.numel(), dtype=dt, device=dev) if want_gnn else None
     gode = torch.zeros(17, dtype=dt, device=dev) if want_gode else None
-    fn = getattr(load(), f"hode_rhs_bwd_{_sfx(dt)}")
-    _check(fn(_stream(), C.c_int(B), _ptr(x), _ptr(t), _ptr(meal), _ptr(tvns), _ptr(gd), _ptr(ode_p), _ptr(nn_p),
-              C.c_int(H), C.c_int(L), _ptr(gout), _ptr(gx), _ptr(gt), _ptr(gnn), _ptr(gode)), "hode_rhs_bwd")
-    return gx, gt, gnn, gode
+    args = [_stream(), C.c_int(B), _ptr(x), _ptr(t), _ptr(meal), _ptr(tvns), _ptr(gd), _ptr(ode_p), _ptr(nn_p),
+            C.c_int(H), C.c_int(L), _ptr(gout), _ptr(gx), _ptr(gt), _ptr(gnn), _ptr(gode)]
+    if want_inputs is None:
+        _check(getattr(load(), f"hode_rhs_bwd_{_sfx(dt)}")(*args), "hode_rhs_bwd")
+        return gx, gt, gnn, gode, None
+    gin = {k: (torch.empty(B, dtype=dt, device=dev) if (u is not None and k in want_inputs) else None)
+           for k, u in zip(INPUT_KEYS, (meal, tvns, gd))}
+    _check(getattr(load(), f"hode_rhs_bwd_inputs_{_sfx(dt)}")(*args, *(_ptr(gin[k]) for k in INPUT_KEYS)), "hode_rhs_bwd_inputs")
+    return gx, gt, gnn, gode, gin
 
 
 def adam_step(p, g, m, v, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=1, max_norm=0.0, grad_scale=1.0,

@@ -42,7 +42,7 @@ def _compute_device() -> torch.device:
 
 
 class _RhsFn(torch.autograd.Function):
-    """ode_residual on the device: K1 forward, K5 backward (grads w.r.t. x, t, MLP and ODE constants)."""
+    """ode_residual on the device: K1 forward, K5 backward (grads w.r.t. x, t, MLP, ODE constants and the inputs meal / tVNS / GD)."""
 
     @staticmethod
     def forward(ctx, x, t, nn_flat, ode_vec, meal, tvns, gd, H, L):
@@ -58,10 +58,15 @@ class _RhsFn(torch.autograd.Function):
         x, t, nn_flat, ode_vec, meal, tvns, gd = ctx.saved_tensors
         H, L, has_m, has_v, has_g = ctx.cfg
         need = ctx.needs_input_grad
-        gx, gt, gnn, gode = hode.rhs_bwd(x, t, meal if has_m else None, tvns if has_v else None,
-                                         gd if has_g else None, ode_vec, nn_flat, H, L, gout.contiguous(),
-                                         want_gt=need[1], want_gnn=need[2], want_gode=need[3])
-        return gx, gt, gnn, gode, None, None, None, None, None
+        ins = (meal if has_m else None, tvns if has_v else None, gd if has_g else None)
+        want_in = tuple(k for k, w in zip(hode.capi.INPUT_KEYS, need[4:7]) if w)
+        if not want_in:
+            gx, gt, gnn, gode = hode.rhs_bwd(x, t, *ins, ode_vec, nn_flat, H, L, gout.contiguous(),
+                                             want_gt=need[1], want_gnn=need[2], want_gode=need[3])
+            return gx, gt, gnn, gode, None, None, None, None, None
+        gx, gt, gnn, gode, gin = hode.rhs_bwd_inputs(x, t, *ins, ode_vec, nn_flat, H, L, gout.contiguous(), want_gt=need[1],
+                                                     want_gnn=need[2], want_gode=need[3], want_inputs=want_in)
+        return (gx, gt, gnn, gode) + tuple(gin[k] for k in hode.capi.INPUT_KEYS) + (None, None)
 
 
 # Stage-tape budget of one autograd solve.  The adjoint reads 6*(L*256 + 32) B per accepted step (1.9 MB per trajectory
@@ -172,7 +177,9 @@ class _Taped:
                 self.y[idx], self.status[idx], self.nsteps[idx], self.nfev[idx] = s2.y, s2.status, s2.nsteps, s2.nfev
         self.n_retried = sum(int(e[0].numel()) for e in extras)
 
-    def backward(self, gy, want_gnn=True, want_gode=False):
+    def backward(self, gy, want_gnn=True, want_gode=False, want_inputs=()):
+        """(gx0, gnn, gode) -- and, when `want_inputs` names any of "meal" / "tVNS" / "GD", a fourth entry: the dict of input
+        gradients of hode.solve_bwd_inputs (rows of the retried trajectories replaced by their own adjoint's)."""
         gy = gy.contiguous()
         subs = []
         if self.extras:
@@ -180,11 +187,16 @@ class _Taped:
             for idx, *_ in self.extras:
                 subs.append(gy[idx].contiguous())
                 gy[idx] = 0                     # the truncated copy in the main launch contributes nothing
-        gx0, gnn, gode = hode.solve_bwd(self.sol, gy, want_gnn=want_gnn, want_gode=want_gode)
+
+        def bwd(sol, g):
+            if not want_inputs:
+                return hode.solve_bwd(sol, g, want_gnn=want_gnn, want_gode=want_gode) + (None,)
+            return hode.solve_bwd_inputs(sol, g, want_gnn=want_gnn, want_gode=want_gode, want_inputs=want_inputs)
+        gx0, gnn, gode, gin = bwd(self.sol, gy)
         for (idx, set_id, sol2, lazy), g2 in zip(self.extras, subs):
             if sol2.tape is not None:
-                g0, gn, go = hode.solve_bwd(sol2, g2, want_gnn=want_gnn, want_gode=want_gode)
-                self._add(gx0, gnn, gode, idx, set_id, g0, gn, go)
+                g0, gn, go, gi = bwd(sol2, g2)
+                self._add(gx0, gnn, gode, idx, set_id, g0, gn, go, gin, gi)
                 continue
             solve, cap = lazy                    # re-integrate with a tape, `cap` trajectories at a time, one buffer
             tape = None
@@ -192,13 +204,16 @@ class _Taped:
                 sl = slice(lo, min(lo + cap, idx.numel()))
                 sp = solve(sl, tape)
                 tape = sp.tape
-                g0, gn, go = hode.solve_bwd(sp, g2[sl].contiguous(), want_gnn=want_gnn, want_gode=want_gode)
-                self._add(gx0, gnn, gode, idx[sl], set_id, g0, gn, go)
-        return gx0, gnn, gode
+                g0, gn, go, gi = bwd(sp, g2[sl].contiguous())
+                self._add(gx0, gnn, gode, idx[sl], set_id, g0, gn, go, gin, gi)
+        return (gx0, gnn, gode) if not want_inputs else (gx0, gnn, gode, gin)
 
     @staticmethod
-    def _add(gx0, gnn, gode, idx, set_id, g0, gn, go):
+    def _add(gx0, gnn, gode, idx, set_id, g0, gn, go, gin=None, gi=None):
         gx0[idx] = g0
+        for k, v in (gi or {}).items():
+            if v is not None:
+                gin[k][idx] = v
         if gn is not None:
             P = gn.numel()
             gnn[P * set_id:P * (set_id + 1)] += gn
@@ -250,7 +265,8 @@ class _SolveFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, nn_flat, ode_vec, t, meal, tvns, gd, H, L, method, rtol, atol, n_sets, info, tape_steps=None):
-        need_tape = any(ctx.needs_input_grad[:3])
+        # (x0, MLP, ODE constants) or the inputs meal / tVNS / GD (positions 4..6)
+        need_tape = any(ctx.needs_input_grad[:3]) or any(ctx.needs_input_grad[4:7])
         B, T = x0.shape[0], t.shape[-1]
         steps = (_small_tape_steps(B, T, method, x0.element_size(), L, H, tape_steps) if need_tape else None) or _tape_steps(T, method, tape_steps)
         per_traj = hode.capi.tape_nbytes(1, steps, x0.element_size(), L, H)
@@ -277,10 +293,12 @@ class _SolveFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         need = ctx.needs_input_grad
+        want_in = tuple(k for k, w in zip(hode.capi.INPUT_KEYS, need[4:7]) if w)
         if not ctx.chunked:
-            gx0, gnn, gode = ctx.sol.backward(gy, want_gnn=need[1], want_gode=need[2])
+            r = ctx.sol.backward(gy, want_gnn=need[1], want_gode=need[2], want_inputs=want_in)
             ctx.sol = None
-            return (gx0 if need[0] else None, gnn, gode) + (None,) * 12
+            gin = r[3] if want_in else {}
+            return (r[0] if need[0] else None, r[1], r[2], None) + tuple(gin.get(k) for k in hode.capi.INPUT_KEYS) + (None,) * 8
         x0, nn_flat, ode_vec, t, meal, tvns, gd, H, L, method, rtol, atol, n_sets, steps, per_traj = ctx.args
         ctx.args = None
         cap = max(1, _tape_budget(x0.device) // per_traj)      # what fits NOW (other tapes may have been freed or made)
@@ -290,6 +308,7 @@ class _SolveFn(torch.autograd.Function):
         gx0 = torch.empty_like(x0)
         gnn = torch.zeros_like(nn_flat) if need[1] else None
         gode = torch.zeros_like(ode_vec) if need[2] else None
+        gin = {k: (torch.empty_like(u) if k in want_in else None) for k, u in zip(hode.capi.INPUT_KEYS, (meal, tvns, gd))}
         # chunk = m whole parameter sets when a set fits the budget, else a slice of one set
         pieces = [(s0 * G + a, (s1 - 1) * G + b, s0, s1) for s0, s1, a, b in _pieces(n_sets, G, cap)]
         tape = None
@@ -299,13 +318,16 @@ class _SolveFn(torch.autograd.Function):
                                cut(gd, lo, hi), ode_vec[17 * s0:17 * s1], nn_flat[P * s0:P * s1], H, L, method, rtol, atol,
                                s1 - s0, steps, tape=tape)
             tape = sol.tape                                              # largest chunk first: later ones fit
-            g0, gn, go = sol.backward(gy[lo:hi], want_gnn=need[1], want_gode=need[2])
+            r = sol.backward(gy[lo:hi], want_gnn=need[1], want_gode=need[2], want_inputs=want_in)
+            g0, gn, go = r[:3]
             gx0[lo:hi] = g0
+            for k in want_in:
+                gin[k][lo:hi] = r[3][k]
             if gn is not None:
                 gnn[P * s0:P * s1] += gn
             if go is not None:
                 gode[17 * s0:17 * s1] += go
-        return (gx0 if need[0] else None, gnn, gode) + (None,) * 12
+        return (gx0 if need[0] else None, gnn, gode, None) + tuple(gin[k] for k in hode.capi.INPUT_KEYS) + (None,) * 8
 
 
 def _allreduce_sum(tensors, group):

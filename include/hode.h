@@ -163,6 +163,44 @@ int hode_solve_bwd_f64(void *stream, int B, int T, const double *t, int t_batche
                        const int32_t *status, void *tape, const double *gy, double *gx0,
                        double *gnn, double *gode);
 
+/* ---- K4 / K5 with input gradients: the derivatives with respect to the external inputs meal, tVNS and GD as well.  The
+ *      exact derivative of what the kernels compute: d f_G / d meal = 1; tVNS enters only the MLP (input column 8 of W1); GD
+ *      enters only k_GE = k_GE0 (1 - GD^g / (IGD_50^g + GD^g)) in dG (zero derivative at GD <= 0).  Step sizes are constants, as
+ *      for every other gradient of the adjoint.
+ *      Every gradient pointer is NULL (not wanted) or, for an input of mode 1, [B], for mode 2, [B,T]; a non-NULL pointer for an
+ *      input of mode 0 (absent / NULL) is HODE_EINVAL.  Input gradients are WRITTEN, not accumulated (like gx0 / gx).
+ *      Solve (hode_solve_bwd_inputs_*): on grid interval k an accepted step evaluates its stages at u(t_s) = u_k + a_s (u_{k+1} - u_k),
+ *      a_s = (t_s - t_k) / (t_{k+1} - t_k); with c_s the stage's input cotangent,
+ *        mode 2:  g[b,k] += (1 - a_s) c_s,  g[b,k+1] += a_s c_s   over every stage of every taped step on interval k;
+ *        mode 1:  g[b] = sum of c_s over every stage of every taped step.
+ *      A grid row that bounds no taped step (rows after a failure, rows inside a run of repeated grid times) is 0.  Each row
+ *      belongs to one trajectory: no atomics, the same call gives the same bits.  gx0 / gnn / gode are those of
+ *      hode_solve_bwd_*: fp64 gx0 the same bits, fp64 gnn / gode the same bits on the tuned shapes (on generic shapes they are summed
+ *      with atomics, equal to rounding as between any two calls); fp32: the request takes the one-role adjoint kernels (the
+ *      wave-specialised and the multi-trajectory kernels have no input gradients), equal to rounding.
+ *      RHS (hode_rhs_bwd_inputs_*): gmeal / gtvns / ggd [B] = (d out[s,:] / d input[s]) . gout[s,:]; the other arguments are
+ *      those of hode_rhs_bwd_*.                                                                                          */
+int hode_solve_bwd_inputs_f32(void *stream, int B, int T, const float *t, int t_batched,
+                              const float *meal, int meal_mode, const float *tvns, int tvns_mode,
+                              const float *gd, int gd_mode, const float *ode_p, const float *nn_p,
+                              int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                              const int32_t *status, void *tape, const float *gy, float *gx0,
+                              float *gnn, float *gode, float *gmeal, float *gtvns, float *ggd);
+int hode_solve_bwd_inputs_f64(void *stream, int B, int T, const double *t, int t_batched,
+                              const double *meal, int meal_mode, const double *tvns, int tvns_mode,
+                              const double *gd, int gd_mode, const double *ode_p, const double *nn_p,
+                              int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                              const int32_t *status, void *tape, const double *gy, double *gx0,
+                              double *gnn, double *gode, double *gmeal, double *gtvns, double *ggd);
+int hode_rhs_bwd_inputs_f32(void *stream, int B, const float *x, const float *t, const float *meal,
+                            const float *tvns, const float *gd, const float *ode_p, const float *nn_p,
+                            int H, int L, const float *gout, float *gx, float *gt, float *gnn, float *gode,
+                            float *gmeal, float *gtvns, float *ggd);
+int hode_rhs_bwd_inputs_f64(void *stream, int B, const double *x, const double *t, const double *meal,
+                            const double *tvns, const double *gd, const double *ode_p, const double *nn_p,
+                            int H, int L, const double *gout, double *gx, double *gt, double *gnn, double *gode,
+                            double *gmeal, double *gtvns, double *ggd);
+
 /* ---- K6: fused global-norm clip + Adam.  Replaces clip_grad_norm_(...,5.0) + torch.optim.Adam
  *      .step() (train/train_hybrid.py:255-261, 438-441).  g is first multiplied by grad_scale
  *      (e.g. 1/world_size after an all-reduce(sum)); max_norm <= 0 disables clipping.
