@@ -127,6 +127,74 @@ int rhs_bwd(void *stream, int B, const R *x, const R *t, const R *meal, const R 
     return launch_rhs_bwd<R>((hipStream_t)stream, a, layers_of(L));
 }
 
+// ---- MCMC (hode_hmc.hip): sizes and pointers checked here, before any launch
+inline bool chains_ok(int C, int D, int ld) { return C >= 1 && D >= 1 && ld >= D && (int64_t)C * ld <= ((int64_t)1 << 40); }
+
+template <typename R> int mse_sets(void *stream, int n_sets, int64_t len, const R *y, const R *obs, R scale, double *loss_sum, R *gy)
+{
+    if (n_sets < 0 || len < 0) return HODE_EINVAL;
+    if (n_sets == 0 || len == 0) return HODE_OK;
+    if (!y || !obs || !loss_sum) return HODE_EINVAL;
+    return launch_mse_sets<R>((hipStream_t)stream, n_sets, len, y, obs, scale, loss_sum, gy);
+}
+
+template <typename R> int hmc_refresh(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, double jitter, const R *minv,
+                                      const double *log_eps, const R *z, const R *g, const double *U, R *p, R *z0, R *g0, double *U0,
+                                      double *ke0, double *eps, int32_t *failed)
+{
+    if (!chains_ok(C, D, ld) || !(jitter >= 0.0 && jitter < 1.0)) return HODE_EINVAL;
+    if (!minv || !log_eps || !z || !g || !U || !p || !z0 || !g0 || !U0 || !ke0 || !eps || !failed) return HODE_EINVAL;
+    HmcRefreshArgs<R> a{C, D, ld, seed, iter, jitter, minv, log_eps, z, g, U, p, z0, g0, U0, ke0, eps, failed};
+    return launch_hmc_refresh<R>((hipStream_t)stream, a);
+}
+
+template <typename R> int hmc_leapfrog(void *stream, int C, int D, int ld, int flags, double kick, const double *eps, const R *minv,
+                                       R *z, R *p, R *g, const R *gnn, const R *gode, int P, const double *loss_sum, double lik_scale,
+                                       const int32_t *status, int n_traj, double *U, double *ke, int32_t *failed, uint32_t ode_mask,
+                                       const double *mu, const double *sd, int sample_nn, R *nn_p, R *ode_p)
+{
+    if (!chains_ok(C, D, ld) || (flags & ~31) || (ode_mask >> 17)) return HODE_EINVAL;
+    const int n_ode = __builtin_popcount(ode_mask);
+    if (P < 0 || (sample_nn && P < 1) || D != n_ode + (sample_nn ? P : 0) || (status && n_traj < 1)) return HODE_EINVAL;
+    if (!eps || !minv || !z || !p || !g) return HODE_EINVAL;
+    if (n_ode && (!mu || !sd)) return HODE_EINVAL;
+    if ((flags & HODE_HMC_ASSEMBLE) && (!U || !failed || (sample_nn && gode && !gnn))) return HODE_EINVAL;
+    if ((flags & HODE_HMC_KE) && !ke) return HODE_EINVAL;
+    if ((flags & (HODE_HMC_DRIFT | HODE_HMC_PARAMS)) && ((n_ode && !ode_p) || (sample_nn && !nn_p))) return HODE_EINVAL;
+    HmcLeapfrogArgs<R> a;
+    a.C = C; a.D = D; a.ld = ld; a.flags = flags; a.P = P; a.n_traj = n_traj; a.n_ode = n_ode; a.sample_nn = sample_nn ? 1 : 0;
+    a.kick = kick; a.lik_scale = lik_scale; a.ode_mask = ode_mask; a.eps = eps; a.minv = minv; a.z = z; a.p = p; a.g = g;
+    a.gnn = gnn; a.gode = gode; a.loss_sum = loss_sum; a.status = status; a.U = U; a.ke = ke; a.failed = failed; a.mu = mu;
+    a.sd = sd; a.nn_p = nn_p; a.ode_p = ode_p;
+    return launch_hmc_leapfrog<R>((hipStream_t)stream, a);
+}
+
+template <typename R> int hmc_accept(void *stream, int C, int D, int ld, int mode, uint64_t seed, uint32_t iter, double target_accept,
+                                     R *z, const R *z0, R *g, const R *g0, double *U, const double *U0, const double *ke0,
+                                     const double *ke, const int32_t *failed, double *log_eps, double *da, int32_t *search, int n_ode,
+                                     const double *mu, const double *sd, R *draws, double *stats, int n_slots, int slot)
+{
+    if (!chains_ok(C, D, ld) || mode < HODE_HMC_SAMPLE || mode > HODE_HMC_DA_FINISH || n_ode < 0 || n_ode > 17 || n_ode > D)
+        return HODE_EINVAL;
+    if (!(target_accept > 0.0 && target_accept < 1.0)) return HODE_EINVAL;
+    if (!z || !z0 || !g || !g0 || !U || !U0 || !ke0 || !ke || !failed || !log_eps || !da || !search) return HODE_EINVAL;
+    if (n_ode && (!mu || !sd)) return HODE_EINVAL;
+    if (slot >= 0 && (slot >= n_slots || !stats)) return HODE_EINVAL;
+    HmcAcceptArgs<R> a;
+    a.C = C; a.D = D; a.ld = ld; a.mode = mode; a.n_ode = n_ode; a.n_slots = n_slots; a.slot = slot < 0 ? -1 : slot;
+    a.seed = seed; a.iter = iter; a.delta = target_accept; a.z = z; a.z0 = z0; a.g = g; a.g0 = g0; a.U = U; a.U0 = U0; a.ke0 = ke0;
+    a.ke = ke; a.failed = failed; a.log_eps = log_eps; a.da = da; a.search = search; a.mu = mu; a.sd = sd; a.draws = draws;
+    a.stats = stats;
+    return launch_hmc_accept<R>((hipStream_t)stream, a);
+}
+
+template <typename R> int hmc_welford(void *stream, int C, int D, int ld, int flags, const R *z, double *wf, R *minv)
+{
+    if (!chains_ok(C, D, ld) || flags < 1 || flags > 3 || !wf) return HODE_EINVAL;
+    if (((flags & HODE_HMC_WELFORD_ACCUM) && !z) || ((flags & HODE_HMC_WELFORD_FINISH) && !minv)) return HODE_EINVAL;
+    return launch_hmc_welford<R>((hipStream_t)stream, C, D, ld, flags, z, wf, minv);
+}
+
 }  // namespace
 
 extern "C" {
@@ -349,5 +417,40 @@ int hode_4gi_window_moments_f64(void *stream, const double *table, int ncols, in
     a.time_div = 1.0; a.row0 = row0; a.N = N; a.S = S;
     return launch_4gi_window_moments((hipStream_t)stream, a, moments, scratch);
 }
+
+// ---- MCMC
+#define HODE_HMC_ABI(SFX, R)                                                                                                             \
+    int hode_mse_sets_##SFX(void *stream, int n_sets, int64_t len, const R *y, const R *obs, R scale, double *loss_sum, R *gy)         \
+    {                                                                                                                                  \
+        return mse_sets<R>(stream, n_sets, len, y, obs, scale, loss_sum, gy);                                                         \
+    }                                                                                                                                  \
+    int hode_hmc_refresh_##SFX(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, double jitter, const R *minv,         \
+                               const double *log_eps, const R *z, const R *g, const double *U, R *p, R *z0, R *g0, double *U0,        \
+                               double *ke0, double *eps, int32_t *failed)                                                             \
+    {                                                                                                                                  \
+        return hmc_refresh<R>(stream, C, D, ld, seed, iter, jitter, minv, log_eps, z, g, U, p, z0, g0, U0, ke0, eps, failed);         \
+    }                                                                                                                                  \
+    int hode_hmc_leapfrog_##SFX(void *stream, int C, int D, int ld, int flags, double kick, const double *eps, const R *minv, R *z,    \
+                                R *p, R *g, const R *gnn, const R *gode, int P, const double *loss_sum, double lik_scale,             \
+                                const int32_t *status, int n_traj, double *U, double *ke, int32_t *failed, uint32_t ode_mask,         \
+                                const double *mu, const double *sd, int sample_nn, R *nn_p, R *ode_p)                                 \
+    {                                                                                                                                  \
+        return hmc_leapfrog<R>(stream, C, D, ld, flags, kick, eps, minv, z, p, g, gnn, gode, P, loss_sum, lik_scale, status, n_traj,  \
+                               U, ke, failed, ode_mask, mu, sd, sample_nn, nn_p, ode_p);                                              \
+    }                                                                                                                                  \
+    int hode_hmc_accept_##SFX(void *stream, int C, int D, int ld, int mode, uint64_t seed, uint32_t iter, double target_accept, R *z,  \
+                              const R *z0, R *g, const R *g0, double *U, const double *U0, const double *ke0, const double *ke,        \
+                              const int32_t *failed, double *log_eps, double *da, int32_t *search, int n_ode, const double *mu,       \
+                              const double *sd, R *draws, double *stats, int n_slots, int slot)                                       \
+    {                                                                                                                                  \
+        return hmc_accept<R>(stream, C, D, ld, mode, seed, iter, target_accept, z, z0, g, g0, U, U0, ke0, ke, failed, log_eps, da,    \
+                             search, n_ode, mu, sd, draws, stats, n_slots, slot);                                                     \
+    }                                                                                                                                  \
+    int hode_hmc_welford_##SFX(void *stream, int C, int D, int ld, int flags, const R *z, double *wf, R *minv)                        \
+    {                                                                                                                                  \
+        return hmc_welford<R>(stream, C, D, ld, flags, z, wf, minv);                                                                  \
+    }
+HODE_HMC_ABI(f32, float)
+HODE_HMC_ABI(f64, double)
 
 }  // extern "C"

@@ -86,6 +86,59 @@ int launch_adam(hipStream_t s, int64_t n, float *p, const float *g, float *m, fl
 int launch_mse(hipStream_t s, int64_t n, const float *y, const float *obs, float scale, double *loss, float *gy);
 int launch_selftest(hipStream_t s, int32_t *out);
 
+// ---- MCMC (hode_hmc.hip): the per-chain passes of multi-chain HMC; chains [C][ld] row-major, see include/hode.h
+template <typename R> int launch_mse_sets(hipStream_t s, int n_sets, int64_t len, const R *y, const R *obs, R scale, double *loss_sum, R *gy);
+template <typename R> struct HmcRefreshArgs {
+    int C, D, ld;
+    uint64_t seed;
+    uint32_t iter;
+    double jitter;
+    const R *minv;
+    const double *log_eps;
+    const R *z, *g;
+    const double *U;
+    R *p, *z0, *g0;
+    double *U0, *ke0, *eps;
+    int32_t *failed;
+};
+template <typename R> struct HmcLeapfrogArgs {
+    int C, D, ld, flags, P, n_traj, n_ode, sample_nn;
+    double kick, lik_scale;
+    uint32_t ode_mask;
+    const double *eps;
+    const R *minv;
+    R *z, *p, *g;
+    const R *gnn, *gode;
+    const double *loss_sum;
+    const int32_t *status;
+    double *U, *ke;
+    int32_t *failed;
+    const double *mu, *sd;
+    R *nn_p, *ode_p;
+};
+template <typename R> struct HmcAcceptArgs {
+    int C, D, ld, mode, n_ode, n_slots, slot;
+    uint64_t seed;
+    uint32_t iter;
+    double delta;
+    R *z;
+    const R *z0;
+    R *g;
+    const R *g0;
+    double *U;
+    const double *U0, *ke0, *ke;
+    const int32_t *failed;
+    double *log_eps, *da;
+    int32_t *search;
+    const double *mu, *sd;
+    R *draws;
+    double *stats;
+};
+template <typename R> int launch_hmc_refresh(hipStream_t s, const HmcRefreshArgs<R> &a);
+template <typename R> int launch_hmc_leapfrog(hipStream_t s, const HmcLeapfrogArgs<R> &a);
+template <typename R> int launch_hmc_accept(hipStream_t s, const HmcAcceptArgs<R> &a);
+template <typename R> int launch_hmc_welford(hipStream_t s, int C, int D, int ld, int flags, const R *z, double *wf, R *minv);
+
 // ---- data side (hode_datagen.hip) ----------------------------------------------------------------------------
 // 4GI model parameters, in the order of include/hode.h (HODE_4GI_NPAR)
 struct FourGIPar {

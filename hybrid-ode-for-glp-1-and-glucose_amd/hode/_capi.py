@@ -22,7 +22,9 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_solve_bwd_f32", "hode_solve_bwd_f64", "hode_adam_step_f32", "hode_mse_fwd_bwd_f32",
            "hode_selftest_xlane", "hode_4gi_default_params", "hode_4gi_generate_f64", "hode_4gi_rhs_f64",
            "hode_4gi_windows_f32", "hode_4gi_window_moments_f64",
-           "hode_solve_bwd_inputs_f32", "hode_solve_bwd_inputs_f64", "hode_rhs_bwd_inputs_f32", "hode_rhs_bwd_inputs_f64"]
+           "hode_solve_bwd_inputs_f32", "hode_solve_bwd_inputs_f64", "hode_rhs_bwd_inputs_f32", "hode_rhs_bwd_inputs_f64",
+           "hode_mse_sets_f32", "hode_mse_sets_f64", "hode_hmc_refresh_f32", "hode_hmc_refresh_f64", "hode_hmc_leapfrog_f32",
+           "hode_hmc_leapfrog_f64", "hode_hmc_accept_f32", "hode_hmc_accept_f64", "hode_hmc_welford_f32", "hode_hmc_welford_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -315,6 +317,60 @@ def mse_fwd_bwd(y, obs, scale, loss_sum=None, want_grad=True):
     _check(load().hode_mse_fwd_bwd_f32(_stream(), C.c_int64(y.numel()), _ptr(y), _ptr(obs), C.c_float(scale),
                                        _ptr(loss_sum), _ptr(gy)), "hode_mse_fwd_bwd")
     return loss_sum, gy
+
+
+# --------------------------------------------------------------------------------------------- MCMC (include/hode.h "MCMC")
+HMC_ASSEMBLE, HMC_KICK, HMC_DRIFT, HMC_KE, HMC_PARAMS = 1, 2, 4, 8, 16
+HMC_SAMPLE, HMC_ADAPT, HMC_SEARCH, HMC_DA_RESTART, HMC_DA_FINISH = 0, 1, 2, 3, 4
+HMC_WELFORD_ACCUM, HMC_WELFORD_FINISH = 1, 2
+
+
+def _real(dt):
+    return C.c_float if dt == torch.float32 else C.c_double
+
+
+def mse_sets(y, obs, scale, loss_sum, want_grad=True):
+    """Per-set sum of squares: y[n_sets, ...] against ONE obs shared by every set (obs.numel() = the per-set length);
+    loss_sum fp64[n_sets] ACCUMULATED, returns gy = 2*scale*(y-obs) (or None)."""
+    _need_gpu(y)
+    y = y.contiguous()
+    n_sets = y.shape[0]
+    obs = obs.to(device=y.device, dtype=y.dtype).contiguous()
+    if y.numel() != n_sets * obs.numel() or loss_sum.dtype != torch.float64 or loss_sum.numel() < n_sets:
+        raise HodeError("mse_sets: y must be [n_sets, len(obs)] and loss_sum fp64[n_sets]")
+    gy = torch.empty_like(y) if want_grad else None
+    _check(getattr(load(), f"hode_mse_sets_{_sfx(y.dtype)}")(_stream(), C.c_int(n_sets), C.c_int64(obs.numel()), _ptr(y), _ptr(obs),
+                                                           _real(y.dtype)(scale), _ptr(loss_sum), _ptr(gy)), "hode_mse_sets")
+    return gy
+
+
+def hmc_refresh(C_, D, ld, seed, it, jitter, minv, log_eps, z, g, U, p, z0, g0, U0, ke0, eps, failed):
+    _check(getattr(load(), f"hode_hmc_refresh_{_sfx(z.dtype)}")(
+        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_uint64(seed), C.c_uint32(it), C.c_double(jitter), _ptr(minv),
+        _ptr(log_eps), _ptr(z), _ptr(g), _ptr(U), _ptr(p), _ptr(z0), _ptr(g0), _ptr(U0), _ptr(ke0), _ptr(eps), _ptr(failed)),
+        "hode_hmc_refresh")
+
+
+def hmc_leapfrog(C_, D, ld, flags, kick, eps, minv, z, p, g, gnn, gode, P, loss_sum, lik_scale, status, n_traj, U, ke, failed,
+                 ode_mask, mu, sd, sample_nn, nn_p, ode_p):
+    _check(getattr(load(), f"hode_hmc_leapfrog_{_sfx(z.dtype)}")(
+        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(flags), C.c_double(kick), _ptr(eps), _ptr(minv), _ptr(z), _ptr(p),
+        _ptr(g), _ptr(gnn), _ptr(gode), C.c_int(P), _ptr(loss_sum), C.c_double(lik_scale), _ptr(status), C.c_int(n_traj), _ptr(U),
+        _ptr(ke), _ptr(failed), C.c_uint32(ode_mask), _ptr(mu), _ptr(sd), C.c_int(int(sample_nn)), _ptr(nn_p), _ptr(ode_p)),
+        "hode_hmc_leapfrog")
+
+
+def hmc_accept(C_, D, ld, mode, seed, it, target_accept, z, z0, g, g0, U, U0, ke0, ke, failed, log_eps, da, search, n_ode, mu, sd,
+               draws=None, stats=None, n_slots=0, slot=-1):
+    _check(getattr(load(), f"hode_hmc_accept_{_sfx(z.dtype)}")(
+        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(mode), C.c_uint64(seed), C.c_uint32(it), C.c_double(target_accept),
+        _ptr(z), _ptr(z0), _ptr(g), _ptr(g0), _ptr(U), _ptr(U0), _ptr(ke0), _ptr(ke), _ptr(failed), _ptr(log_eps), _ptr(da),
+        _ptr(search), C.c_int(n_ode), _ptr(mu), _ptr(sd), _ptr(draws), _ptr(stats), C.c_int(n_slots), C.c_int(slot)), "hode_hmc_accept")
+
+
+def hmc_welford(C_, D, ld, flags, z, wf, minv):
+    _check(getattr(load(), f"hode_hmc_welford_{_sfx(minv.dtype)}")(
+        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(flags), _ptr(z), _ptr(wf), _ptr(minv)), "hode_hmc_welford")
 
 
 # --------------------------------------------------------------------------------------------- data side

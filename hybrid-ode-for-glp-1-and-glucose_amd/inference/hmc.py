@@ -1,0 +1,400 @@
+"""Multi-chain Hamiltonian Monte Carlo over a HybridODENN on the GPU: `run_hmc`, the replacement for the reference's
+`run_nuts` (inference/mcmc.py:17-173, a one-chain random-walk placeholder that samples its prior).
+
+Target (the density run_nuts intends, mcmc.py:50-98): a Gaussian likelihood with fixed noise_sigma over one batch dict
+{initial_state, observations, time_points, external_inputs}; Gaussian priors on the sampled mechanistic constants (the
+reference's seven by default) and N(0, 1) on every MLP weight.  The chains move in prior-standardised coordinates z
+(theta_ode = mu + sd z, theta_nn = z), so the identity is a sensible first mass matrix.
+
+Static-trajectory HMC with C independent chains: each leapfrog step is ONE forward solve with tape + ONE adjoint over all
+C x N trajectories (the C positions ride in the kernels' parameter-set dimension), the per-chain sum of squares and its
+cotangent come from hode_mse_sets, and everything else a step does to the chains (momentum, kicks, drifts, the Metropolis
+test, dual averaging, draws, the mass matrix) is a HIP kernel of csrc/hode_hmc.hip.  Step sizes are per chain (dual
+averaging, Stan's constants), the diagonal mass matrix is pooled across chains over Stan's doubling warm-up windows."""
+import math
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+import hode
+
+__all__ = ["run_hmc", "HMCResult", "REFERENCE_PRIORS"]
+
+# reference inference/mcmc.py:60-68
+REFERENCE_PRIORS = {"a_GI": (0.0104, 0.002), "k_I": (0.025, 0.005), "rho": (0.003, 0.001), "E_max": (0.1, 0.02),
+                    "V_max": (9.0, 2.0), "K_m": (7.0, 1.5), "k_L": (0.02, 0.005)}
+
+_SEARCH_ITER = 0x80000000        # Philox iteration words of the step-size search trials (sampling uses 0, 1, 2, ...)
+_INIT_ITER = 0xFFFFFFFF          # ... and of the initial jitter
+_MAX_SEARCH = 20
+
+
+def _windows(num_warmup):
+    """Stan's warm-up: (init buffer, [(start, end) of the slow windows]); 75 / 25-doubling / 50, or 15 % / 75 % / 10 %."""
+    if num_warmup < 20:
+        return num_warmup, []
+    if num_warmup >= 150:
+        init, term, base = 75, 50, 25
+    else:
+        init, term = int(0.15 * num_warmup), int(0.1 * num_warmup)
+        base = num_warmup - init - term
+    end, out, start, w = num_warmup - term, [], init, base
+    while start < end:
+        if start + 3 * w > end:
+            w = end - start
+        out.append((start, start + w))
+        start += w
+        w *= 2
+    return init, out
+
+
+class _Sampler:
+    """Device state of C chains and the three passes of an iteration (refresh, L leapfrog steps, accept).  Tests drive it
+    directly; run_hmc is the schedule around it."""
+
+    def __init__(self, model, data, n_chains, noise_sigma=1.0, ode_priors=None, sample_nn=True, seed=0, solver="dopri5",
+                 rtol=1e-6, atol=1e-8, dtype=torch.float32, jitter=0.1):
+        from models.hybrid_ode_nn import _SOLVERS, _compute_device
+        from models.ode_core import ODE_PARAM_NAMES
+        model._check_supported()
+        self.model, self.dt = model, dtype
+        dev = self.dev = _compute_device()
+        nl = model.nn_residual
+        self.H, self.L = nl.hidden_dim, nl.hip_layers
+        self.P = hode.n_params(self.H, self.L)
+        self.method = _SOLVERS.get(str(solver).lower())
+        if self.method is None:
+            raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+        self.rtol, self.atol, self.seed, self.jitter = float(rtol), float(atol), int(seed) & (2 ** 64 - 1), float(jitter)
+        priors = dict(REFERENCE_PRIORS if ode_priors is None else ode_priors)
+        for k in priors:
+            if k not in ODE_PARAM_NAMES:
+                raise ValueError(f"unknown mechanistic constant {k!r}; known: {list(ODE_PARAM_NAMES)}")
+        self.ode_names = [n for n in ODE_PARAM_NAMES if n in priors]           # ascending ODE index = z order
+        self.ode_mask = sum(1 << ODE_PARAM_NAMES.index(n) for n in self.ode_names)
+        self.n_ode, self.sample_nn = len(self.ode_names), bool(sample_nn)
+        self.nn_names = [(n, tuple(p.shape)) for n, p in nl.named_parameters()]
+        self.D = self.n_ode + (self.P if self.sample_nn else 0)
+        if self.D == 0:
+            raise ValueError("nothing to sample: no ode_priors and sample_nn=False")
+        self.ld = (self.D + 3) // 4 * 4
+        C = self.C = int(n_chains)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.mu = torch.tensor([float(priors[n][0]) for n in self.ode_names] or [0.0], **f64)
+        self.sd = torch.tensor([float(priors[n][1]) for n in self.ode_names] or [1.0], **f64)
+        with torch.no_grad():
+            nn0, ode0 = model._params_on(dev)
+        self.nn_base, self.ode_base = nn0.detach().to(dtype).contiguous(), ode0.detach().to(dtype).contiguous()
+        self.nn_p = self.nn_base.repeat(C).contiguous()
+        self.ode_p = self.ode_base.repeat(C).contiguous()
+        R = dict(dtype=dtype, device=dev)
+        z = torch.zeros(C, self.ld, **R)
+        for i, n in enumerate(self.ode_names):
+            z[:, i] = (float(self.ode_base[ODE_PARAM_NAMES.index(n)]) - float(self.mu[i])) / float(self.sd[i])
+        if self.sample_nn:
+            z[:, self.n_ode:self.D] = self.nn_base
+        self.z, self.p, self.g = z, torch.zeros(C, self.ld, **R), torch.zeros(C, self.ld, **R)
+        self.z0, self.g0 = torch.zeros_like(z), torch.zeros_like(z)
+        self.minv = torch.ones(self.ld, **R)
+        self.U, self.U0, self.ke, self.ke0 = (torch.zeros(C, **f64) for _ in range(4))
+        self.eps, self.log_eps = torch.zeros(C, **f64), torch.zeros(C, **f64)
+        self.da = torch.zeros(C, 4, **f64)
+        self.search = torch.zeros(C, 2, dtype=torch.int32, device=dev)
+        self.failed = torch.zeros(C, dtype=torch.int32, device=dev)
+        self.wf = torch.zeros(3, self.D, **f64)
+        self.lik_scale = 0.5 / float(noise_sigma) ** 2
+        self.loss_sum = torch.zeros(C, **f64)
+        self.has_data = data is not None
+        if self.has_data:
+            x0, t, ins = model._prep_inputs(data["initial_state"], data["time_points"], data.get("external_inputs"), dev)
+            cast = lambda v: None if v is None else v.to(dtype).contiguous()              # noqa: E731
+            self.x0, self.t = cast(x0), cast(t)
+            self.meal, self.tvns, self.gd = cast(ins["meal"]), cast(ins["tVNS"]), cast(ins["GD"])
+            self.N, self.T = self.x0.shape[0], self.t.shape[-1]
+            self.obs = data["observations"].to(dev, dtype).reshape(self.N, -1).contiguous()
+            if self.obs.shape[1] != self.T * 6:
+                raise ValueError("observations must be [B, T, 6] on the grid of time_points")
+            self.status = torch.zeros(C, self.N, dtype=torch.int32, device=dev)
+        self.gnn = self.gode = None
+
+    # ------------------------------------------------------------------ the pieces of an iteration
+    def evaluate(self):
+        """Likelihood sum of squares, its gradient and the solve statuses at the parameters in nn_p / ode_p (all chains):
+        forward with tape -> hode_mse_sets -> adjoint, cut into tape-budget pieces the way _gauss_lik_core cuts them."""
+        if not self.has_data:
+            return
+        from models.hybrid_ode_nn import _pieces, _small_tape_steps, _solve_taped, _tape_budget, _tape_steps
+        C, N, T, P = self.C, self.N, self.T, self.P
+        elem = self.x0.element_size()
+        ts = self.model.tape_steps
+        steps = _small_tape_steps(C * N, T, self.method, elem, self.L, self.H, ts) or _tape_steps(T, self.method, ts)
+        per_traj = hode.capi.tape_nbytes(1, steps, elem, self.L, self.H)
+        cap = max(1, _tape_budget(self.dev, C * N * per_traj) // per_traj)
+        pieces = _pieces(C, N, cap)
+        one = len(pieces) == 1
+        self.loss_sum.zero_()
+        want_nn, want_ode = self.sample_nn, self.n_ode > 0
+        if not one:
+            self.gnn = torch.zeros(C * P, dtype=self.dt, device=self.dev) if want_nn else None
+            self.gode = torch.zeros(C * 17, dtype=self.dt, device=self.dev) if want_ode else None
+        tape = None
+        for s0, s1, lo, hi in pieces:
+            m = s1 - s0
+            rep = lambda v: None if v is None else (v[lo:hi].repeat(m, *([1] * (v.dim() - 1))) if m > 1 else v[lo:hi])  # noqa: E731
+            sol = _solve_taped(rep(self.x0), self.t if self.t.dim() == 1 else rep(self.t), rep(self.meal), rep(self.tvns), rep(self.gd),
+                               self.ode_p[17 * s0:17 * s1], self.nn_p[P * s0:P * s1], self.H, self.L, self.method, self.rtol,
+                               self.atol, m, steps, tape=tape)
+            tape = sol.tape
+            gy = hode.capi.mse_sets(sol.y.view(m, -1), self.obs[lo:hi], self.lik_scale, self.loss_sum[s0:s1])
+            _, gn, go = sol.backward(gy.view_as(sol.y), want_gnn=want_nn, want_gode=want_ode)
+            if one:
+                self.gnn, self.gode = gn, go
+                self.status = sol.status.view(C, N)
+            else:
+                if gn is not None:
+                    self.gnn[P * s0:P * s1] += gn
+                if go is not None:
+                    self.gode[17 * s0:17 * s1] += go
+                self.status[s0:s1, lo:hi] = sol.status.view(m, hi - lo)
+
+    def leapfrog(self, flags, kick=0.0):
+        d = self.has_data
+        hode.capi.hmc_leapfrog(self.C, self.D, self.ld, flags, kick, self.eps, self.minv, self.z, self.p, self.g,
+                               self.gnn if d else None, self.gode if d else None, self.P, self.loss_sum if d else None, self.lik_scale,
+                               self.status if d else None, self.N if d else 0, self.U, self.ke, self.failed, self.ode_mask, self.mu,
+                               self.sd, self.sample_nn, self.nn_p, self.ode_p)
+
+    def refresh(self, it, jitter=None):
+        hode.capi.hmc_refresh(self.C, self.D, self.ld, self.seed, it, self.jitter if jitter is None else jitter, self.minv, self.log_eps,
+                              self.z, self.g, self.U, self.p, self.z0, self.g0, self.U0, self.ke0, self.eps, self.failed)
+
+    def trajectory(self, n_leapfrog):
+        """L leapfrog steps from (z, p) with the chains' eps: kick/2, (drift, gradient, kick) x L with the last kick halved."""
+        A, K, Dr, E = hode.capi.HMC_ASSEMBLE, hode.capi.HMC_KICK, hode.capi.HMC_DRIFT, hode.capi.HMC_KE
+        self.leapfrog(K | Dr, 0.5)
+        for i in range(n_leapfrog):
+            self.evaluate()
+            last = i == n_leapfrog - 1
+            self.leapfrog(A | K | (E if last else Dr), 0.5 if last else 1.0)
+
+    def accept(self, mode, it, target_accept=0.8, draws=None, stats=None, n_slots=0, slot=-1):
+        hode.capi.hmc_accept(self.C, self.D, self.ld, mode, self.seed, it, target_accept, self.z, self.z0, self.g, self.g0, self.U,
+                             self.U0, self.ke0, self.ke, self.failed, self.log_eps, self.da, self.search, self.n_ode, self.mu, self.sd,
+                             draws, stats, n_slots, slot)
+
+    def gradient(self):
+        """U and grad U at z (after moving z by hand): parameters -> solve -> assembly."""
+        self.leapfrog(hode.capi.HMC_PARAMS)
+        self.evaluate()
+        self.failed.zero_()
+        self.leapfrog(hode.capi.HMC_ASSEMBLE)
+
+    def initial_jitter(self):
+        """The reference's start (mcmc.py:101-113): MLP weights + 0.01 N(0,1); sampled constants + 0.1 sd N(0,1)."""
+        self.refresh(_INIT_ITER, 0.0)                 # p = xi (minv = 1): the chain's own normals
+        scale = torch.full((self.ld,), 0.01, dtype=self.dt, device=self.dev)
+        scale[:self.n_ode] = 0.1
+        scale[self.D:] = 0
+        self.z.addcmul_(self.p, scale)
+
+    def find_step_size(self, window):
+        """Stan's initial step-size heuristic for every chain at once: one trial = one leapfrog step of all chains, at most
+        _MAX_SEARCH trials; then dual averaging restarts from the found step (mu = log(10 eps))."""
+        self.search.zero_()
+        for k in range(_MAX_SEARCH):
+            it = _SEARCH_ITER + 64 * window + k
+            self.refresh(it, 0.0)
+            self.trajectory(1)
+            self.accept(hode.capi.HMC_SEARCH, it)
+            if bool(self.search[:, 1].all()):
+                break
+        self.accept(hode.capi.HMC_DA_RESTART, 0)
+
+    def welford(self, flags):
+        hode.capi.hmc_welford(self.C, self.D, self.ld, flags, self.z, self.wf, self.minv)
+
+
+# ---------------------------------------------------------------------------------------------------- diagnostics
+def _split(x):
+    """[M, N, ...] -> [2M, N // 2, ...] (the two halves of every chain)."""
+    n = x.shape[1] // 2
+    return torch.cat([x[:, :n], x[:, x.shape[1] - n:]], 0)
+
+
+def _rhat(x):
+    x = _split(x.double())
+    n = x.shape[1]
+    means = x.mean(1)
+    W = x.var(1, unbiased=True).mean(0)
+    B = n * means.var(0, unbiased=True)
+    var_plus = (n - 1) / n * W + B / n
+    return torch.sqrt(var_plus / W)
+
+
+def _ess(x):
+    """Multi-chain ESS of every coordinate (Geyer's initial monotone sequence, Vehtari et al. 2021), x [M, N, K]."""
+    x = x.double()
+    M, N = x.shape[:2]
+    xc = x - x.mean(1, keepdim=True)
+    f = torch.fft.rfft(xc, n=2 * N, dim=1)
+    acov = torch.fft.irfft(f * f.conj(), n=2 * N, dim=1)[:, :N] / N                  # [M, N, K], biased
+    mean_var = acov[:, 0].mean(0) * N / (N - 1)
+    var_plus = mean_var * (N - 1) / N + (x.mean(1).var(0, unbiased=True) if M > 1 else 0)
+    rho = 1.0 - (mean_var - acov.mean(0)) / var_plus                                  # [N, K]
+    rho[0] = 1.0
+    npair = N // 2
+    Pk = rho[:2 * npair].reshape(npair, 2, -1).sum(1)                                 # [npair, K]
+    keep = torch.cumprod((Pk > 0).to(torch.int64), 0).bool()                          # initial positive sequence
+    Pk = torch.where(keep, Pk, torch.zeros_like(Pk))
+    Pk = torch.cummin(Pk, 0).values                                                   # ... made monotone
+    tau = -1.0 + 2.0 * (Pk * keep).sum(0)
+    tau = torch.clamp(tau, min=1.0 / math.log10(M * N) if M * N > 10 else 1e-3)
+    return M * N / tau
+
+
+def _rank_normal(x):
+    """Rank-normalised draws (ranks over all chains and draws, Blom's offset) for the bulk ESS."""
+    M, N = x.shape[:2]
+    flat = x.reshape(M * N, -1)
+    r = torch.argsort(torch.argsort(flat, 0), 0).double() + 1.0
+    return torch.special.ndtri((r - 0.375) / (M * N + 0.25)).reshape(x.shape)
+
+
+# ---------------------------------------------------------------------------------------------------- result
+class HMCResult:
+    """Draws of run_hmc.  `samples`: numpy arrays keyed like the reference's draws (`ode.<name>`, `nn.<parameter name>`),
+    shaped [chains, draws, ...]; `flat()`: the same as [chains * draws, ...] (what reference posterior_summary takes);
+    `stats`: accept_prob / log_posterior / divergent / failed_solve [chains, draws], step_size [chains], inv_mass [D];
+    `rhat()` / `ess()`: split R-hat and multi-chain bulk ESS of every coordinate; `predict(...)`: posterior predictive."""
+
+    def __init__(self, draws, ode_names, nn_names, stats, model=None, ode_base=None, nn_base=None):
+        self.draws = draws                          # [C, n, D] natural coordinates (device or CPU tensor)
+        self.ode_names, self.nn_names = list(ode_names), list(nn_names)
+        self.stats = stats
+        self.model, self.ode_base, self.nn_base = model, ode_base, nn_base
+        self._samples = None
+
+    @property
+    def n_chains(self):
+        return self.draws.shape[0]
+
+    @property
+    def n_draws(self):
+        return self.draws.shape[1]
+
+    @property
+    def samples(self) -> Dict[str, np.ndarray]:
+        if self._samples is None:
+            d = self.draws.detach().cpu().numpy()
+            C, n = d.shape[:2]
+            out, off = {}, 0
+            for name in self.ode_names:
+                out[f"ode.{name}"] = d[:, :, off].copy()
+                off += 1
+            for name, shape in self.nn_names:
+                k = int(np.prod(shape))
+                if off + k > d.shape[2]:
+                    break
+                out[f"nn.{name}"] = d[:, :, off:off + k].reshape(C, n, *shape).copy()
+                off += k
+            self._samples = out
+        return self._samples
+
+    def flat(self) -> Dict[str, np.ndarray]:
+        return {k: v.reshape(v.shape[0] * v.shape[1], *v.shape[2:]) for k, v in self.samples.items()}
+
+    def rhat(self) -> torch.Tensor:
+        """Split R-hat of every coordinate, [D] (fp64, on the draws' device)."""
+        return _rhat(self.draws)
+
+    def ess(self, kind="bulk") -> torch.Tensor:
+        """Multi-chain ESS of every coordinate, [D], over split chains with Geyer's initial monotone sequence: "bulk" on the
+        rank-normalised draws (Vehtari et al. 2021), "mean" on the draws themselves (the ESS of the posterior mean's MCSE)."""
+        x = self.draws.double()
+        return _ess(_split(_rank_normal(x) if kind == "bulk" else x))
+
+    def _param_sets(self, thin=1):
+        from models.ode_core import ODE_PARAM_NAMES
+        d = self.draws[:, ::thin].reshape(-1, self.draws.shape[2]).to(torch.float32)
+        S = d.shape[0]
+        n_ode = len(self.ode_names)
+        ode = self.ode_base.to(d.device, torch.float32).reshape(1, 17).repeat(S, 1)
+        for i, n in enumerate(self.ode_names):
+            ode[:, ODE_PARAM_NAMES.index(n)] = d[:, i]
+        P = self.nn_base.numel()
+        nn = d[:, n_ode:n_ode + P] if d.shape[1] >= n_ode + P else self.nn_base.to(d.device, torch.float32).reshape(1, P).repeat(S, 1)
+        return S, nn.contiguous().reshape(-1), ode.reshape(-1).contiguous()
+
+    def predict(self, initial_state, t_span, external_inputs=None, thin=1, solver="dopri5", rtol=1e-6, atol=1e-8):
+        """Posterior predictive of the kept draws (every `thin`-th of each chain), ONE batched solve -> [n_draws, B, T, 6]."""
+        if self.model is None:
+            raise ValueError("this result carries no model (built from arrays)")
+        m = self.model
+        S, nn_flat, ode_vec = self._param_sets(thin)
+        x0 = initial_state.unsqueeze(0) if initial_state.dim() == 1 else initial_state
+        B = x0.shape[0]
+        rep = lambda v: None if v is None else torch.as_tensor(v).repeat(*([S] + [1] * (torch.as_tensor(v).dim() - 1)))  # noqa: E731
+        t = torch.as_tensor(t_span)
+        u = {k: rep(v) for k, v in (external_inputs or {}).items() if torch.as_tensor(v).dim() >= 1 and torch.as_tensor(v).numel() > 1}
+        for k, v in (external_inputs or {}).items():
+            if k not in u:
+                u[k] = v
+        with torch.no_grad():
+            y = m._solve(x0.repeat(S, 1), rep(t) if t.dim() == 2 else t, u, solver, rtol, atol, n_sets=S, nn_flat=nn_flat,
+                         ode_vec=ode_vec, differentiable=False)
+        m._warn_failures(m.last_solve_info)
+        return y.reshape(S, B, y.shape[1], 6).to(m.device)
+
+
+# ---------------------------------------------------------------------------------------------------- entry point
+def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1000, num_warmup: int = 500, n_chains: int = 64,
+            n_leapfrog: int = 16, target_accept: float = 0.8, noise_sigma: float = 1.0,
+            ode_priors: Optional[Dict[str, Tuple[float, float]]] = None, sample_nn: bool = True, thin: int = 1, seed: int = 0,
+            solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8, device=None, dtype=torch.float32,
+            jitter: float = 0.1, progress=None) -> HMCResult:
+    """Sample the posterior of `model` given the batch `data` (None: the prior alone) with n_chains chains.
+
+    num_warmup iterations adapt the per-chain step size (dual averaging to target_accept) and the pooled diagonal mass matrix
+    (Stan's windows); then num_samples iterations, every `thin`-th kept.  ode_priors: name -> (mean, std) of the sampled
+    mechanistic constants (default: the reference's seven); sample_nn: sample every MLP weight (prior N(0, 1)).  `device` is
+    accepted for run_nuts compatibility: the work runs on the HIP device.  `progress(it, stats)`, if given, is called once per
+    iteration (one host synchronisation)."""
+    if num_samples < 1 or num_warmup < 0 or n_chains < 1 or n_leapfrog < 1 or thin < 1:
+        raise ValueError("num_samples, n_chains, n_leapfrog, thin must be >= 1 and num_warmup >= 0")
+    if not 0.0 < target_accept < 1.0:
+        raise ValueError("target_accept must lie in (0, 1)")
+    s = _Sampler(model, data, n_chains, noise_sigma, ode_priors, sample_nn, seed, solver, rtol, atol, dtype, jitter)
+    C, D = s.C, s.D
+    n_slots = (num_samples + thin - 1) // thin
+    draws = torch.empty(C, n_slots, D, dtype=dtype, device=s.dev)
+    stats = torch.empty(C, n_slots, 4, dtype=torch.float64, device=s.dev)
+    cap = hode.capi
+    s.initial_jitter()
+    s.gradient()
+    window = 0
+    s.find_step_size(window)
+    init, wins = _windows(num_warmup)
+    ends = {b: a for a, b in wins}
+    for it in range(num_warmup + num_samples):
+        warm = it < num_warmup
+        slot = -1
+        if not warm and (it - num_warmup) % thin == 0:
+            slot = (it - num_warmup) // thin
+        s.refresh(it)
+        s.trajectory(n_leapfrog)
+        s.accept(cap.HMC_ADAPT if warm else cap.HMC_SAMPLE, it, target_accept, draws, stats, n_slots, slot)
+        if warm and any(a <= it < b for a, b in wins):
+            s.welford(cap.HMC_WELFORD_ACCUM)
+        if warm and (it + 1) in ends:
+            s.welford(cap.HMC_WELFORD_FINISH)          # new M^-1, then a new step size and a fresh dual averaging
+            window += 1
+            s.find_step_size(window)
+        if warm and it + 1 == num_warmup:
+            s.accept(cap.HMC_DA_FINISH, it)
+        if progress is not None:
+            progress(it, {"step_size": s.log_eps.exp().mean().item()})
+    st = {"accept_prob": stats[..., 0].cpu().numpy(), "log_posterior": stats[..., 1].cpu().numpy(),
+          "divergent": stats[..., 2].cpu().numpy() > 0, "failed_solve": stats[..., 3].cpu().numpy() > 0,
+          "step_size": s.log_eps.exp().cpu().numpy(), "inv_mass": s.minv[:D].double().cpu().numpy()}
+    return HMCResult(draws, s.ode_names, s.nn_names if sample_nn else [], st, model, s.ode_base, s.nn_base)

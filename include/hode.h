@@ -274,6 +274,90 @@ int hode_4gi_window_moments_f64(void *stream, const double *table, int ncols, in
                                 int col_glucagon, int col_glp1, int col_ge, int col_ffa, const int64_t *row0, int64_t N,
                                 int64_t S, double *moments, void *scratch);
 
+/* =====================================================================================================
+ * MCMC: the per-chain passes of multi-chain Hamiltonian Monte Carlo (inference/hmc.py, run_hmc).  Replaces the
+ * random-walk placeholder of the reference's inference/mcmc.py:17-173 (run_nuts).
+ *
+ * The driver evaluates U(z) = scale * sum (y - obs)^2 + |z|^2 / 2 for C chains at once: the forward solve and the adjoint
+ * (hode_solve_fwd_* / hode_solve_bwd_*) run with n_sets = C, hode_mse_sets_* gives every chain its own sum and cotangent.
+ * Everything else a sampling iteration does to the chains' state is these kernels.
+ *   - pointers: DEVICE memory, except where noted; `stream` as everywhere in this header; HODE_EINVAL for a bad size or a
+ *     NULL that is not allowed, checked on the host before any launch;
+ *   - chains: C rows of `ld` reals (ld >= D), row c at offset c * ld: z (position), p (momentum), g (grad U), z0 / g0 (the
+ *     trajectory's start); minv[ld] = the diagonal of M^-1, shared by all chains.  ld % 4 == 0 and 16-byte aligned rows let
+ *     every lane move four coordinates per 16-byte access; the padding (D <= d < ld) must hold 0 in z and 1 in minv;
+ *   - coordinates of z (prior-standardised): d < n_ode = popcount(ode_mask) are the sampled mechanistic constants in ascending
+ *     ODE-index order (bit k of ode_mask = ode_p[k]), theta = mu[d] + sd[d] z[d] (mu, sd: fp64 [n_ode], the Gaussian priors);
+ *     then, with sample_nn, the P MLP weights in nn_p order, theta = z (prior N(0, 1)).  D = n_ode + (sample_nn ? P : 0);
+ *   - per-chain scalars are fp64 [C]: U, U0, ke, ke0 (energies), eps (this trajectory's step), log_eps (the adapted one);
+ *     failed: int32 [C];
+ *   - random numbers: Philox4x32-10, key (seed bits 0..31, chain), counter (coordinate / 4, stream, iter, seed bits 32..63):
+ *     a chain's draws do not depend on C or on the launch geometry;
+ *   - no floating-point atomics: every chain sum is taken in a fixed order, the same call gives the same bits.
+ * ===================================================================================================== */
+#define HODE_HMC_ASSEMBLE 1 /* leapfrog flags: g = likelihood gradient (gnn, gode) + z; U = lik_scale * loss_sum + |z|^2 / 2;
+                               failed |= any status != 0 of the chain's n_traj trajectories */
+#define HODE_HMC_KICK 2     /* p -= kick * eps * g */
+#define HODE_HMC_DRIFT 4    /* z += eps * minv * p, then write the sampled entries of nn_p / ode_p (natural coordinates) */
+#define HODE_HMC_KE 8       /* ke = p^T minv p / 2 (after the kick) */
+#define HODE_HMC_PARAMS 16  /* write the sampled entries of nn_p / ode_p from z without moving */
+#define HODE_HMC_SAMPLE 0     /* accept modes: Metropolis test, restore (z0, g0, U0) on reject */
+#define HODE_HMC_ADAPT 1      /*   the same + one dual-averaging update of log_eps (gamma 0.05, t0 10, kappa 0.75) */
+#define HODE_HMC_SEARCH 2     /*   one trial of the initial step-size search (double / halve to one-step acceptance 0.8); always restores */
+#define HODE_HMC_DA_RESTART 3 /*   restart dual averaging: mu = log(10 eps), clear the search state */
+#define HODE_HMC_DA_FINISH 4  /*   log_eps = the averaged log step (end of warm-up) */
+#define HODE_HMC_WELFORD_ACCUM 1  /* welford flags: add z of every chain, chains in order */
+#define HODE_HMC_WELFORD_FINISH 2 /* minv = n/(n+5) var + 1e-3 * 5/(n+5) (Stan), then reset the accumulators */
+
+/* ---- per-set sum of squares and cotangent.  y[n_sets][len] (set s = one chain's trajectories), obs[len] ONE copy shared by
+ *      every set (obs index = element index modulo len); loss_sum: double[n_sets], ACCUMULATED (a set split over several calls
+ *      sums to its whole); gy[n_sets][len] = 2 * scale * (y - obs) (may be NULL).  Unaligned pointers and any len are fine. */
+int hode_mse_sets_f32(void *stream, int n_sets, int64_t len, const float *y, const float *obs, float scale,
+                      double *loss_sum, float *gy);
+int hode_mse_sets_f64(void *stream, int n_sets, int64_t len, const double *y, const double *obs, double scale,
+                      double *loss_sum, double *gy);
+
+/* ---- trajectory start: p = M^{1/2} xi (xi ~ N(0, 1), stream `iter`), ke0 = p^T minv p / 2, z0 = z, g0 = g, U0 = U,
+ *      eps = exp(log_eps) * (1 + jitter * (2u - 1)) (u uniform, same stream), failed = 0. */
+int hode_hmc_refresh_f32(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, double jitter, const float *minv,
+                         const double *log_eps, const float *z, const float *g, const double *U, float *p, float *z0,
+                         float *g0, double *U0, double *ke0, double *eps, int32_t *failed);
+int hode_hmc_refresh_f64(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, double jitter, const double *minv,
+                         const double *log_eps, const double *z, const double *g, const double *U, double *p, double *z0,
+                         double *g0, double *U0, double *ke0, double *eps, int32_t *failed);
+
+/* ---- one leapfrog pass (HODE_HMC_* flags, applied in the order assemble, kick, ke, drift, params).  gnn[C][P] / gode[C][17]:
+ *      the adjoint's per-set gradients of scale * sum (y - obs)^2 (NULL: no likelihood term), loss_sum[C] its value (NULL: 0);
+ *      status[C][n_traj]: the solve's (NULL: none); nn_p[C][P] / ode_p[C][17]: the parameters of the next solve, only the sampled
+ *      entries are written.  A NULL that a set flag needs is HODE_EINVAL. */
+int hode_hmc_leapfrog_f32(void *stream, int C, int D, int ld, int flags, double kick, const double *eps, const float *minv,
+                          float *z, float *p, float *g, const float *gnn, const float *gode, int P, const double *loss_sum,
+                          double lik_scale, const int32_t *status, int n_traj, double *U, double *ke, int32_t *failed,
+                          uint32_t ode_mask, const double *mu, const double *sd, int sample_nn, float *nn_p, float *ode_p);
+int hode_hmc_leapfrog_f64(void *stream, int C, int D, int ld, int flags, double kick, const double *eps, const double *minv,
+                          double *z, double *p, double *g, const double *gnn, const double *gode, int P, const double *loss_sum,
+                          double lik_scale, const int32_t *status, int n_traj, double *U, double *ke, int32_t *failed,
+                          uint32_t ode_mask, const double *mu, const double *sd, int sample_nn, double *nn_p, double *ode_p);
+
+/* ---- end of a trajectory (mode HODE_HMC_*).  H = U + ke; divergent = failed, H1 not finite or H1 - H0 > 1000 (accept
+ *      probability 0); a rejected proposal restores z, g, U from z0, g0, U0.  da: fp64 [C][4] dual-averaging state {mu, log eps
+ *      bar, H bar, t}; search: int32 [C][2] {direction, done}.  slot >= 0 (sample modes) stores the kept state:
+ *      draws[C][n_slots][D] in natural coordinates (may be NULL), stats[C][n_slots][4] = {accept probability, log posterior
+ *      (-U, up to a constant), divergent, failed solve}. */
+int hode_hmc_accept_f32(void *stream, int C, int D, int ld, int mode, uint64_t seed, uint32_t iter, double target_accept,
+                        float *z, const float *z0, float *g, const float *g0, double *U, const double *U0, const double *ke0,
+                        const double *ke, const int32_t *failed, double *log_eps, double *da, int32_t *search, int n_ode,
+                        const double *mu, const double *sd, float *draws, double *stats, int n_slots, int slot);
+int hode_hmc_accept_f64(void *stream, int C, int D, int ld, int mode, uint64_t seed, uint32_t iter, double target_accept,
+                        double *z, const double *z0, double *g, const double *g0, double *U, const double *U0, const double *ke0,
+                        const double *ke, const int32_t *failed, double *log_eps, double *da, int32_t *search, int n_ode,
+                        const double *mu, const double *sd, double *draws, double *stats, int n_slots, int slot);
+
+/* ---- pooled cross-chain variance of every coordinate (the diagonal mass matrix of a slow warm-up window).
+ *      wf: fp64 [3][D] = {count, mean, M2} per coordinate, zero it before the first window. */
+int hode_hmc_welford_f32(void *stream, int C, int D, int ld, int flags, const float *z, double *wf, float *minv);
+int hode_hmc_welford_f64(void *stream, int C, int D, int ld, int flags, const double *z, double *wf, double *minv);
+
 #ifdef __cplusplus
 }
 #endif
