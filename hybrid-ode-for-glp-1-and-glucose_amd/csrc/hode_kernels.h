@@ -40,6 +40,19 @@ template <typename R> struct AdjInArgs : AdjArgs<R> {
     R *gmeal, *gtvns, *ggd;
 };
 
+// tangent-linear pass over the tape (hode_solve_jvp.hip).  The external inputs are not arguments: the tape holds what the
+// stages used (activations, stage state, the step's interval constants); gd_mode selects the Hill-term instantiation.
+template <typename R> struct JvpArgs {
+    int B, T, t_batched, gd_mode, n_sets, H, P, max_steps, K;
+    const R *t, *ode_p, *nn_p;
+    const int32_t *nsteps, *status;
+    const R *tape;
+    const int32_t *tape_seg;
+    const R *tape_stage;
+    const R *v_ode, *v_x0;  // [n_sets][K][17] / [B][K][6], either may be NULL
+    R *dy;                  // [B][K][T][6]
+};
+
 template <typename R> struct RhsArgs {
     int B, H, P;
     const R *x, *t, *meal, *tvns, *gd, *ode_p, *nn_p;
@@ -65,6 +78,8 @@ template <typename R> int launch_solve_bwd_inputs(hipStream_t s, const AdjInArgs
 int launch_solve_bwd_ws(hipStream_t s, const AdjArgs<float> &a, int L, int method, int cus);
 // second pass of the gradient reduction: rows of a.partials added in workgroup order (hode_solve_bwd.hip)
 void launch_adj_reduce(hipStream_t s, const float *partials, int rowlen, int blocks_per_set, int n_sets, int P, float *gnn, float *gode);
+// tangent-linear solve (hode_solve_jvp.hip; tuned shapes, every dtype)
+template <typename R> int launch_solve_jvp(hipStream_t s, const JvpArgs<R> &a, int L, int method);
 template <typename R> int launch_rhs_fwd(hipStream_t s, const RhsArgs<R> &a, int L);
 template <typename R> int launch_rhs_bwd(hipStream_t s, const RhsArgs<R> &a, int L);
 // generic network path (hode_generic.hip): H <= 128, L <= 8, weights streamed from L2

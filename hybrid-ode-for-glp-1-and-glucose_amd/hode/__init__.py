@@ -7,6 +7,7 @@ CPU / eager fallback -- if the library or a GPU is missing the calls raise.
 from . import _build as build_info  # noqa: F401
 from . import _capi as capi  # noqa: F401
 from ._capi import (METHOD_DP54, METHOD_RK4, HodeError, adam_step, lib_path, load, mse_fwd_bwd, n_params,  # noqa: F401
-                    rhs_bwd, rhs_bwd_inputs, rhs_fwd, selftest_xlane, solve_bwd, solve_bwd_inputs, solve_fwd, version)
+                    rhs_bwd, rhs_bwd_inputs, rhs_fwd, selftest_xlane, solve_bwd, solve_bwd_inputs, solve_fwd, solve_jvp,
+                    version)
 from . import train  # noqa: F401,E402
 from . import datagen  # noqa: F401,E402

@@ -24,7 +24,8 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_4gi_windows_f32", "hode_4gi_window_moments_f64",
            "hode_solve_bwd_inputs_f32", "hode_solve_bwd_inputs_f64", "hode_rhs_bwd_inputs_f32", "hode_rhs_bwd_inputs_f64",
            "hode_mse_sets_f32", "hode_mse_sets_f64", "hode_hmc_refresh_f32", "hode_hmc_refresh_f64", "hode_hmc_leapfrog_f32",
-           "hode_hmc_leapfrog_f64", "hode_hmc_accept_f32", "hode_hmc_accept_f64", "hode_hmc_welford_f32", "hode_hmc_welford_f64"]
+           "hode_hmc_leapfrog_f64", "hode_hmc_accept_f32", "hode_hmc_accept_f64", "hode_hmc_welford_f32", "hode_hmc_welford_f64",
+           "hode_solve_jvp_f32", "hode_solve_jvp_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -253,6 +254,36 @@ def _solve_bwd(sol, gy, want_gnn, want_gode, want_inputs):
     _check(getattr(load(), f"hode_solve_bwd_inputs_{_sfx(dt)}")(*args, *(_ptr(gin[k]) for k in INPUT_KEYS)),
            "hode_solve_bwd_inputs")
     return gx0, gnn, gode, gin
+
+
+def solve_jvp(sol, v_ode=None, v_x0=None):
+    """Tangent-linear pass over the tape of `sol` (made with want_tape=True; hode_solve_jvp_*, include/hode.h).
+    v_ode [n_sets,K,17] (directions in the ODE constants of each parameter set) and/or v_x0 [B,K,6] (in the initial states).
+    Returns dy[B,K,T,6] = (dy/d ode_p) v_ode + (dy/d x0) v_x0 -- the exact derivative of the discrete scheme the forward ran."""
+    if sol.tape is None:
+        raise HodeError("solve_jvp needs a solution computed with want_tape=True")
+    if v_ode is None and v_x0 is None:
+        raise HodeError("solve_jvp needs v_ode and/or v_x0")
+    t, t_batched, meal, tvns, gd, ode_p, nn_p, n_sets, H, L, method = sol.ctx
+    dt, dev = sol.y.dtype, sol.y.device
+    B, T = sol.y.shape[:2]
+    v_ode, v_x0 = _prep(v_ode, dt, dev), _prep(v_x0, dt, dev)
+    ref = v_ode if v_ode is not None else v_x0
+    if ref.dim() != 3:
+        raise HodeError("directions must be [n_sets,K,17] / [B,K,6]")
+    K = ref.shape[1]
+    if v_ode is not None and tuple(v_ode.shape) != (n_sets, K, 17):
+        raise HodeError(f"v_ode must be [n_sets,K,17]=({n_sets},K,17), got {tuple(v_ode.shape)}")
+    if v_x0 is not None and tuple(v_x0.shape) != (B, K, 6):
+        raise HodeError(f"v_x0 must be [B,K,6]=({B},K,6), got {tuple(v_x0.shape)}")
+    dy = torch.empty(B, K, T, 6, dtype=dt, device=dev)
+    fn = getattr(load(), f"hode_solve_jvp_{_sfx(dt)}")
+    _check(fn(_stream(), C.c_int(B), C.c_int(T), _ptr(t), C.c_int(t_batched),
+              _ptr(meal), C.c_int(_mode(meal, B, T)), _ptr(tvns), C.c_int(_mode(tvns, B, T)),
+              _ptr(gd), C.c_int(_mode(gd, B, T)), _ptr(ode_p), _ptr(nn_p), C.c_int(n_sets), C.c_int(H), C.c_int(L),
+              C.c_int(method), C.c_int(sol.max_steps), _ptr(sol.nsteps), _ptr(sol.status), _ptr(sol.tape), C.c_int(K),
+              _ptr(v_ode), _ptr(v_x0), _ptr(dy)), "hode_solve_jvp")
+    return dy
 
 
 def rhs_bwd(x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, want_gt=False, want_gnn=True, want_gode=False):

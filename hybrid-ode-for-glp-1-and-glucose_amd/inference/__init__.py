@@ -19,9 +19,10 @@ import importlib.abc
 import os
 import sys
 
+from .calibrate import CalibrationResult, fit_patients
 from .vi import VariationalInference
 
-__all__ = ["VariationalInference", "run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results"]
+__all__ = ["VariationalInference", "fit_patients", "CalibrationResult", "run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results"]
 
 _MCMC_NAMES = ("run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results")
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -28,6 +28,11 @@ from .ode_core import ODE_PARAM_NAMES, ODECore
 
 logger = logging.getLogger(__name__)
 
+# ODECore's state vector (the columns of y) and the constants sensitivities() differentiates by default: the seven the
+# reference treats as uncertain (inference/mcmc.py:60-68, inference.hmc.REFERENCE_PRIORS)
+STATE_NAMES = ("G", "I", "Glu", "GLP1", "GE", "FFA")
+SENSITIVITY_DEFAULT_WRT = ("a_GI", "k_I", "rho", "E_max", "V_max", "K_m", "k_L")
+
 # reference hybrid_ode_nn.py:174-181 maps these names onto SciPy methods ('dopri5' silently means
 # DOP853 there).  Every adaptive name runs the DP5(4) kernel here: all of them converge to the same
 # solution, and DP5(4) is what 'dopri5'/'rk45' name.  'rk4' = fixed step, one step per interval.
@@ -893,6 +898,73 @@ class HybridODENN(nn.Module):
         self._warn_failures(self.last_solve_info)
         y = y.reshape(S, B, y.shape[1], 6).to(self.device)
         return y[:, 0] if single else y
+
+    # ------------------------------------------------------------------ forward-mode sensitivities
+    def sensitivities(self, initial_state: torch.Tensor, t_span: torch.Tensor,
+                      external_inputs: Optional[Dict[str, torch.Tensor]] = None,
+                      wrt: Tuple[str, ...] = SENSITIVITY_DEFAULT_WRT, ode_sets: Optional[Dict[str, torch.Tensor]] = None,
+                      solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8, dtype=torch.float32,
+                      max_steps: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Trajectories and their Jacobian columns: (y [B,T,6], S [B,K,T,6]) with S[:, k] = d y / d wrt[k].
+
+        `wrt` names ODECore constants (with or without the `ode_` prefix) or initial-state components `x0:<state>`
+        (G, I, Glu, GLP1, GE, FFA).  One taped forward solve and one tangent-linear pass over its tape (hode.solve_jvp): the
+        exact derivative of the discrete scheme the solve ran, step sizes held constant.  `ode_sets` optionally gives the
+        constants per patient (name -> [B]; names not given keep the model's value): the B patients then run as B parameter
+        sets, each with its own copy of the network.  No-grad; rows after a failed solve (status in last_solve_info) are 0."""
+        self._check_supported()
+        dev = _compute_device()
+        single = initial_state.dim() == 1
+        x0, t, ins = self._prep_inputs(initial_state.unsqueeze(0) if single else initial_state, t_span, external_inputs, dev)
+        B, T = x0.shape[0], t.shape[-1]
+        cast = lambda v: None if v is None else v.to(dtype).contiguous()                          # noqa: E731
+        cols = []
+        for name in wrt:
+            if name.startswith("x0:"):
+                if name[3:] not in STATE_NAMES:
+                    raise ValueError(f"unknown state {name[3:]!r}; known: {list(STATE_NAMES)}")
+                cols.append(("x0", STATE_NAMES.index(name[3:])))
+            else:
+                key = name[4:] if name.startswith("ode_") else name
+                if key not in ODE_PARAM_NAMES:
+                    raise ValueError(f"unknown mechanistic constant {name!r}; known: {list(ODE_PARAM_NAMES)} or x0:<state>")
+                cols.append(("ode", ODE_PARAM_NAMES.index(key)))
+        if not cols:
+            raise ValueError("sensitivities needs at least one entry in wrt")
+        method = _SOLVERS.get(str(solver).lower())
+        if method is None:
+            raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+        nl = self.nn_residual
+        H, L = nl.hidden_dim, nl.hip_layers
+        with torch.no_grad():
+            nn_flat, ode_vec = self._params_on(dev)
+            nn_flat, ode_vec = cast(nn_flat.detach()), cast(ode_vec.detach())
+            n_sets = 1
+            if ode_sets:
+                ode_mat = ode_vec.reshape(1, 17).repeat(B, 1)
+                for name, vals in ode_sets.items():
+                    key = name[4:] if name.startswith("ode_") else name
+                    if key not in ODE_PARAM_NAMES:
+                        raise ValueError(f"unknown mechanistic constant {name!r}; known: {list(ODE_PARAM_NAMES)}")
+                    ode_mat[:, ODE_PARAM_NAMES.index(key)] = torch.as_tensor(vals).to(dev, dtype).reshape(-1).expand(B)
+                ode_vec, nn_flat, n_sets = ode_mat.reshape(-1).contiguous(), nn_flat.repeat(B).contiguous(), B
+            if max_steps is None:
+                max_steps = (_small_tape_steps(B, T, method, torch.finfo(dtype).bits // 8, L, H, self.tape_steps)
+                             or _tape_steps(T, method, self.tape_steps))
+            sol = hode.solve_fwd(cast(x0), cast(t), cast(ins["meal"]), cast(ins["tVNS"]), cast(ins["GD"]), ode_vec, nn_flat, H, L,
+                                 method=method, rtol=float(rtol), atol=float(atol), max_steps=int(max_steps), n_sets=n_sets,
+                                 want_tape=True)
+            K = len(cols)
+            v_ode = torch.zeros(n_sets, K, 17, dtype=dtype, device=dev)
+            v_x0 = torch.zeros(B, K, 6, dtype=dtype, device=dev)
+            for k, (kind, j) in enumerate(cols):
+                (v_ode if kind == "ode" else v_x0)[:, k, j] = 1.0
+            has_ode, has_x0 = any(c[0] == "ode" for c in cols), any(c[0] == "x0" for c in cols)
+            S = hode.solve_jvp(sol, v_ode if has_ode else None, v_x0 if has_x0 else None)
+        self.last_solve_info = {"status": sol.status, "nsteps": sol.nsteps, "nfev": sol.nfev}
+        self._warn_failures(self.last_solve_info)
+        y, S = sol.y.to(self.device), S.to(self.device)
+        return (y[0], S[0]) if single else (y, S)
 
     # ------------------------------------------------------------------ ELBO (BASELINE config 5)
     def elbo(self, batch: Dict[str, torch.Tensor], n_samples: int = 16, noise_sigma: float = 0.1,

@@ -192,6 +192,37 @@ int hode_solve_bwd_inputs_f64(void *stream, int B, int T, const double *t, int t
                               int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
                               const int32_t *status, void *tape, const double *gy, double *gx0,
                               double *gnn, double *gode, double *gmeal, double *gtvns, double *ggd);
+/* ---- K6: tangent-linear (forward-mode) solve over the tape of the forward -- the sensitivities of a trajectory with respect to
+ *      a few directions (no reference counterpart: the reference has no sensitivities; per-patient calibration needs them).
+ *      For K directions per trajectory
+ *        dy[b,k,:,:] = (d y_b / d ode_p) v_ode[set(b),k,:] + (d y_b / d x0_b) v_x0[b,k,:]
+ *      v_ode [n_sets][K][17] and v_x0 [B][K][6]: either may be NULL (that part is 0), not both; dy [B][K][T][6] is WRITTEN.
+ *      The exact derivative of the discrete scheme the forward ran: the taped accepted steps with their step sizes held
+ *      constant, the same tableau and grid breaks; ReLU' = (taped activation > 0); GD enters through k_GE (zero derivative of the
+ *      Hill term's constants at GD <= 0, as in the adjoint).  The arguments up to `tape` are those of hode_solve_bwd_* for the
+ *      same tape, which is READ ONLY here: the same tape may be walked again by this call or by the adjoint.
+ *      Rows follow y exactly: row 0 = v_x0; a grid row is the tangent at the end of the step that closes its interval; a
+ *      repeated grid time copies the row before it; rows after a failure (status 1-3) are 0, as in y.  Non-finite tangents are
+ *      returned as computed; status is the forward's.
+ *      Duality: this pass and hode_solve_bwd_* differentiate the same discrete map, so for any gy
+ *        <gy, dy>  ==  <gx0, v_x0> + <gode, v_ode>       to rounding (gx0, gode of hode_solve_bwd_* with the same gy).
+ *      One trajectory per wavefront, no atomics: the same call gives the same bits, and a K-direction call gives the bits of K
+ *      one-direction calls.  Any K >= 1 (tiled internally).
+ *      Envelope: the tuned shapes (H <= 64, L <= 4, ReLU), fp32 and fp64, both methods, every input mode, batched or shared
+ *      grids.  HODE_EUNSUPPORTED for larger or non-ReLU networks and for HODE_LAYERS_NN_SHARED; HODE_EINVAL for K < 1, no
+ *      direction, or the argument rules of hode_solve_bwd_* -- all checked before any launch.                              */
+int hode_solve_jvp_f32(void *stream, int B, int T, const float *t, int t_batched,
+                       const float *meal, int meal_mode, const float *tvns, int tvns_mode,
+                       const float *gd, int gd_mode, const float *ode_p, const float *nn_p,
+                       int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                       const int32_t *status, const void *tape, int K, const float *v_ode,
+                       const float *v_x0, float *dy);
+int hode_solve_jvp_f64(void *stream, int B, int T, const double *t, int t_batched,
+                       const double *meal, int meal_mode, const double *tvns, int tvns_mode,
+                       const double *gd, int gd_mode, const double *ode_p, const double *nn_p,
+                       int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                       const int32_t *status, const void *tape, int K, const double *v_ode,
+                       const double *v_x0, double *dy);
 int hode_rhs_bwd_inputs_f32(void *stream, int B, const float *x, const float *t, const float *meal,
                             const float *tvns, const float *gd, const float *ode_p, const float *nn_p,
                             int H, int L, const float *gout, float *gx, float *gt, float *gnn, float *gode,
