@@ -2,23 +2,27 @@
 """bench.py -- headline benchmark of the hot path (BASELINE.json): patient-trajectories/s of the
 batched 6-state DP5(4) solve (ODE + 4x64 MLP residual, fp32, T = 241 grid points = 240 intervals).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
 
 One process per GPU.  A "step" is one pass of the hot path over one synthetic cohort shard
 (BASELINE config[1]: 4 096 patients per GPU, forward solve).  Inputs are resident in HBM before
 the timed region.  Weak scaling: every rank integrates its own 4 096-patient shard, no data-path
-collective in the forward path.  After the headline region the same shard is pushed through the
-TRAINING step of config[2]/[3] (forward with tape -> fused MSE -> adjoint -> one RCCL all-reduce
-of the 54 KB gradient buffer -> fused clip+Adam) and reported under "train_step".
+collective in the forward path.
 
-At N = 1 two more legs follow: "vi_step" (BASELINE config 5 at its per-GPU size: 8 192 patients x 16 VI draws, ELBO +
-reparameterised gradient + Adam) and "data_side" (65 536-subject 4GI cohort generation + dataset windows).
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, --dump-outputs, and ONE JSON line
+from rank 0.  Its `roofline` prices the timed kernel against the fp32 compute peak (the binding roof: ~5 000 flop/byte,
+SURVEY.md 8d) and also carries the HBM reading; both come from the timed steps, no run of their own.
 
-Rank 0 prints ONE JSON line.  `roofline` prices the solve kernel against the fp32 compute peak
-(the binding roof: ~5 000 flop/byte, SURVEY.md 8d) and also carries the HBM reading;
-`cpu_baseline` times the oracle (C port of the same algorithm) on the host cores, N = 1 only.
+--full adds the secondary legs after the headline region, each dropped again by its --no-* option:
+  * "zscore_regime": the same solve from z-scored initial states (rank 0);
+  * "train_step": the same shard through the TRAINING step of config[2]/[3] (forward with tape -> fused MSE -> adjoint ->
+    one RCCL all-reduce of the 54 KB gradient buffer -> fused clip+Adam), with the per-kernel rooflines of that step;
+  * at N = 1: "vi_step" (BASELINE config 5 at its per-GPU size: 8 192 patients x 16 VI draws, ELBO + reparameterised
+    gradient + Adam), "generic_path" (the 128 x 5 network), "data_side" (65 536-subject 4GI cohort generation
+    + dataset windows), "sobol" (the reference's Sobol study), "class_path" (the drop-in classes) and "cpu_baseline" (the
+    reference-style loop and the C oracle on the host cores, plus the parity of the HIP path with both).
 """
 import argparse
 import json
@@ -91,16 +95,19 @@ def measured_traffic(key):
     return d.get(key), d.get("source")
 
 
-def ensure_built(may_build=True):
+def ensure_built(may_build=True, oracle=True):
     """Build BEFORE any GPU / collective call when libhode.so is missing OR was linked from other sources than the ones in this
     tree (csrc/Makefile stamps the binary with a hash of its sources; hode/_build.py compares) -- a stale binary is never
     benchmarked.  Every rank takes the same path: an exclusive file lock, then `make` (the Makefile links to a temporary name
     and renames it, so no rank can dlopen a half-written library).  may_build=False (--no-build / HODE_NO_BUILD=1; every
     invocation under rocprofv3, where the profiler's tool library has initialised the GPU before Python starts and a child
-    process must not be spawned): a missing or stale artefact is an error instead."""
+    process must not be spawned): a missing or stale artefact is an error instead.  oracle=False (a plain run: only the
+    --full legs use the C oracle) leaves oracle/ alone."""
     import subprocess
     from hode import _build
     _build.ensure(may_build=may_build)
+    if not oracle:
+        return
     osoname = os.path.join(ROOT, "oracle", "_build", "libhode_oracle.so")
     srcs = [os.path.join(ROOT, "oracle", f) for f in ("hode_oracle.c", "hode_oracle_impl.h", "fourgi_oracle.c")]
     if not os.path.exists(osoname) or any(os.path.getmtime(f) > os.path.getmtime(osoname) for f in srcs if os.path.exists(f)):
@@ -577,13 +584,16 @@ def dump_outputs(out_dir, sol, max_bytes=DUMP_MAX_BYTES, seed=0):
         np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--patients-per-gpu", type=int, default=0, help="default: 4 096 (BASELINE config[1] per GPU); with --gpus 8 "
                     "8 192 = BASELINE config[3], the 65 536-patient cohort over the node")
+    ap.add_argument("--full", action="store_true", help="after the headline, run the secondary legs too (CPU baselines and "
+                    "parity, z-scored regime, training step, VI, generic path, data side, Sobol study, class path); --no-cpu-baseline, "
+                    "--no-zscore, --no-train, --no-vi, --no-generic, --no-data-side, --no-sobol and --no-class-path drop one leg each")
     ap.add_argument("--train-steps", type=int, default=5)
     ap.add_argument("--cpu-sample", type=int, default=32768, help="trajectories of the C-oracle leg of cpu_baseline")
     ap.add_argument("--ref-sample", type=int, default=1024, help="trajectories of the reference-style (solve_ivp loop) leg")
@@ -604,10 +614,26 @@ def main():
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, default) | gloo (rehearsal: ranks may share one GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
                     "returned (y, status, nsteps, nfev of rank 0's shard) as DIR/<name>.npy, for output-by-output comparison of builds")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         raise SystemExit("--steps must be >= 1")
+    return args
 
+
+def secondary_legs(args, world):
+    """The legs a run adds to the headline: none without --full; with it, every leg its --no-* option leaves -- "zscore" and
+    "train" at any N, the others at N = 1 only.  All but "train" (every rank) run on rank 0."""
+    if not args.full:
+        return set()
+    want = {"zscore": not args.no_zscore, "train": not args.no_train}
+    if world == 1:
+        want.update(cpu_baseline=not args.no_cpu_baseline, vi=not args.no_vi, generic=not args.no_generic,
+                    data_side=not args.no_data_side, sobol=not args.no_sobol, class_path=not args.no_class_path)
+    return {k for k, on in want.items() if on}
+
+
+def main():
+    args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -615,13 +641,14 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if args.gpus > 1 and world == 1:
         raise SystemExit("for --gpus N > 1 launch with torch.distributed.run (one rank per GPU)")
-    ensure_built(may_build=not (args.no_build or os.environ.get("HODE_NO_BUILD")))   # before any GPU / collective call
+    legs = secondary_legs(args, world)
+    ensure_built(may_build=not (args.no_build or os.environ.get("HODE_NO_BUILD")), oracle=args.full)   # before any GPU / collective call
     if args.patients_per_gpu <= 0:
         args.patients_per_gpu = 8192 if args.gpus == 8 else 4096
     # the host-only half of cpu_baseline (reference-style solve_ivp loops: one thread, then one spawned worker process per core;
     # the C oracle on threads) runs BEFORE the first call that initialises the GPU: no process is started from a GPU-initialised one
     host = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and "cpu_baseline" in legs:
         host = cpu_baseline_host(args.cpu_sample, args.ref_sample)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
@@ -695,7 +722,7 @@ def main():
     # ------------------------------------------------------------------ secondary: z-scored regime
     # what GlucoseDataset(normalize=True) actually feeds (train/train_hybrid.py:139): x0 ~ N(0,1)^6
     zs = None
-    if rank == 0 and not args.no_zscore:
+    if rank == 0 and "zscore" in legs:
         xz = torch.randn(B, 6, generator=torch.Generator().manual_seed(4242)).to(dev)
         zsol = hode.solve_fwd(xz, t, meal, tvns, None, ode, nn_teacher, H, L, rtol=1e-6, atol=1e-8)
         torch.cuda.synchronize()
@@ -715,7 +742,7 @@ def main():
 
     # ------------------------------------------------------------------ secondary: training step
     train = None
-    if not args.no_train:
+    if "train" in legs:
         obs, student = train_problem(dev, x0, t, meal, tvns, ode, nn_teacher, rank)
         state = hode.train.TrainState(student.clone())
         n_glob = B_total * T * 6
@@ -817,15 +844,15 @@ def main():
             out["zscore_regime"] = zs
         if train is not None:
             out["train_step"] = train
-        if world == 1 and not args.no_vi:
+        if "vi" in legs:
             out["vi_step"] = vi_step(dev, args.vi_patients)
-        if world == 1 and not args.no_generic:
+        if "generic" in legs:
             out["generic_path"] = generic_path(dev)
-        if world == 1 and not args.no_data_side:
+        if "data_side" in legs:
             out["data_side"] = data_side(dev, args.cohort, cpu=not args.no_cpu_baseline)
-        if world == 1 and not args.no_sobol:
+        if "sobol" in legs:
             out["sobol"] = sobol_leg(dev, host=host)
-        if world == 1 and not args.no_class_path:
+        if "class_path" in legs:
             out["class_path"] = class_path(dev, x0, t, meal, tvns, kern_ms)
         if host is not None:
             host.pop("sobol_reference_style", None)

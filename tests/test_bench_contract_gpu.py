@@ -28,7 +28,7 @@ def test_bench_two_ranks_gloo_on_one_gpu_matches_single_process_step():
     B = 256
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--patients-per-gpu", str(B), "--train-steps", "2"]
+           "--backend", "gloo", "--patients-per-gpu", str(B), "--train-steps", "2", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -68,7 +68,7 @@ def test_bench_two_ranks_uneven_shards_is_the_single_process_step_on_the_whole_c
     N = 37
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--total-patients", str(N), "--train-steps", "2", "--no-zscore"]
+           "--backend", "gloo", "--total-patients", str(N), "--train-steps", "2", "--no-zscore", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -179,3 +179,21 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     assert np.allclose(y, sol.y.cpu().numpy(), rtol=1e-6, atol=1e-7)
     assert np.array_equal(np.load(out_dir / "status.npy"), sol.status.cpu().numpy().astype(np.float64))
     assert np.array_equal(np.load(out_dir / "nsteps.npy"), sol.nsteps.cpu().numpy().astype(np.float64))
+
+
+def test_bench_plain_run_prints_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line and nothing else -- no secondary leg, no
+    CPU baseline -- with the same fields and arithmetic as a --full run's headline."""
+    B = 128
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--patients-per-gpu", str(B)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert set(out) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                        "vs_baseline", "dtype", "data", "config", "roofline"}
+    assert out["metric"] == "patient-trajectories/s (6-state, 240-step dopri5)" and out["unit"] == "patient-trajectories/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 2 and out["warmup"] == 1
+    assert abs(out["value"] - B * 2 / (out["ms_per_step"] * 2e-3)) < 1e-6 * out["value"]
+    assert out["config"]["trajectories_ok"] == B and 0 < out["roofline"]["frac"] < 1

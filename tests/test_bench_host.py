@@ -115,3 +115,17 @@ def test_dump_outputs_writes_the_solution_and_samples_fixed_rows_when_too_large(
     assert sum(os.path.getsize(a / f) for f in os.listdir(a)) <= cap
     assert np.array_equal(np.load(a / "y.npy"), sol.y.numpy()[rows])
     assert np.array_equal(np.load(a / "nfev.npy"), sol.nfev.numpy()[rows].astype(np.float64))
+
+
+def test_plain_run_has_no_secondary_legs_and_full_has_them_all():
+    """bench.py without --full times the headline and nothing else; --full adds every leg its --no-* options leave, the N = 1
+    legs only when one process runs."""
+    import bench
+    base = ["--gpus", "1", "--steps", "5", "--warmup", "2"]
+    assert bench.secondary_legs(bench.parse_args(base), 1) == set()
+    assert bench.secondary_legs(bench.parse_args(base + ["--no-train", "--no-sobol"]), 1) == set()
+    full = bench.secondary_legs(bench.parse_args(base + ["--full"]), 1)
+    assert full == {"zscore", "train", "cpu_baseline", "vi", "generic", "data_side", "sobol", "class_path"}
+    assert bench.secondary_legs(bench.parse_args(base + ["--full", "--no-train", "--no-sobol"]), 1) == full - {"train", "sobol"}
+    assert bench.secondary_legs(bench.parse_args(["--gpus", "2", "--full"]), 2) == {"zscore", "train"}
+    assert bench.secondary_legs(bench.parse_args(["--gpus", "2", "--full", "--no-zscore"]), 2) == {"train"}

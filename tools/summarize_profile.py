@@ -25,7 +25,7 @@ if len(stats) > 1:
              "the run, or the stale files -- the counters of different kernel versions would be averaged together")
 rows = list(csv.DictReader(open(stats[-1])))
 with open(os.path.join(dst, f"{tag}_kernel_stats.csv"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 40 --warmup 5 --train-steps 20 --no-cpu-baseline --no-vi --no-generic --no-zscore --no-sobol --no-class-path --no-build\n")
+    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 40 --warmup 5 --train-steps 20 --no-cpu-baseline --no-vi --no-generic --no-zscore --no-sobol --no-class-path --no-build\n")
     f.write("kernel,calls,total_ns,avg_ns,pct,min_ns,max_ns\n")
     for r in rows[:18]:
         f.write(f"\"{short(r['Name'])[:90]}\",{r['Calls']},{r['TotalDurationNs']},{float(r['AverageNs']):.0f},{r['Percentage']},{r['MinNs']},{r['MaxNs']}\n")
@@ -48,7 +48,7 @@ for fcsv in glob.glob(os.path.join(src, "pmc_*", "*", "*_counter_collection.csv"
             for c, v in d.items():
                 pmc[k][c] = sum(v) / len(v)
             pmc[k].setdefault("_launches", len(next(iter(d.values()))))
-out = {"command": "rocprofv3 --pmc <group> -- python3 bench.py --steps 12 --warmup 3 --train-steps 12 --no-cpu-baseline ...",
+out = {"command": "rocprofv3 --pmc <group> -- python3 bench.py --full --steps 12 --warmup 3 --train-steps 12 --no-cpu-baseline ...",
        "note": "per-launch averages; one rocprofv3 run per counter group (FETCH_SIZE and WRITE_SIZE in separate passes)",
        "kernels": pmc}
 traffic = {}
