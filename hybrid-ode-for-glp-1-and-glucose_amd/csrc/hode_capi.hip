@@ -221,6 +221,64 @@ template <typename R> int hmc_welford(void *stream, int C, int D, int ld, int fl
     return launch_hmc_welford<R>((hipStream_t)stream, C, D, ld, flags, z, wf, minv);
 }
 
+// ---- No-U-Turn sampling (hode_nuts.hip)
+template <typename R> int nuts_begin(void *stream, int C, int D, int ld, const R *z, const R *p, const R *g, const double *U, const double *U0,
+                                     const double *ke0, R *tree, double *dst, int32_t *ist)
+{
+    if (!chains_ok(C, D, ld)) return HODE_EINVAL;
+    if (!z || !p || !g || !U || !U0 || !ke0 || !tree || !dst || !ist) return HODE_EINVAL;
+    return launch_nuts_begin<R>((hipStream_t)stream, C, D, ld, z, p, g, U, U0, ke0, tree, dst, ist);
+}
+
+template <typename R> int nuts_pre(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, const double *eps, const R *minv,
+                                   R *tree, int32_t *ist, const int32_t *rank, uint32_t ode_mask, const double *mu, const double *sd,
+                                   int sample_nn, int P, R *nn_p, R *ode_p)
+{
+    if (!chains_ok(C, D, ld) || (ode_mask >> 17)) return HODE_EINVAL;
+    const int n_ode = __builtin_popcount(ode_mask);
+    if (P < 0 || (sample_nn && P < 1) || D != n_ode + (sample_nn ? P : 0)) return HODE_EINVAL;
+    if (!eps || !minv || !tree || !ist || !rank) return HODE_EINVAL;
+    if (n_ode && ode_p && (!mu || !sd)) return HODE_EINVAL;
+    NutsPreArgs<R> a;
+    a.C = C; a.D = D; a.ld = ld; a.n_ode = n_ode; a.sample_nn = sample_nn ? 1 : 0; a.P = P; a.seed = seed; a.iter = iter;
+    a.ode_mask = ode_mask; a.eps = eps; a.minv = minv; a.tree = tree; a.ist = ist; a.rank = rank; a.mu = mu; a.sd = sd;
+    a.nn_p = nn_p; a.ode_p = ode_p;
+    return launch_nuts_pre<R>((hipStream_t)stream, a);
+}
+
+template <typename R> int nuts_post(void *stream, int C, int D, int ld, int max_depth, uint64_t seed, uint32_t iter, const double *eps,
+                                    const R *minv, R *tree, R *ckpt, double *dst, int32_t *ist, const int32_t *rank, const R *gnn,
+                                    const R *gode, int P, const double *loss_sum, double lik_scale, const int32_t *status, int n_traj,
+                                    uint32_t ode_mask, const double *sd, int sample_nn)
+{
+    if (!chains_ok(C, D, ld) || max_depth < 1 || max_depth > HODE_NUTS_MAX_DEPTH || (ode_mask >> 17)) return HODE_EINVAL;
+    const int n_ode = __builtin_popcount(ode_mask);
+    if (P < 0 || (sample_nn && P < 1) || D != n_ode + (sample_nn ? P : 0) || (status && n_traj < 1)) return HODE_EINVAL;
+    if (!eps || !minv || !tree || !ckpt || !dst || !ist || !rank) return HODE_EINVAL;
+    if ((n_ode && gode && !sd) || (sample_nn && gode && !gnn)) return HODE_EINVAL;
+    NutsPostArgs<R> a;
+    a.C = C; a.D = D; a.ld = ld; a.max_depth = max_depth; a.n_ode = n_ode; a.P = P; a.n_traj = n_traj; a.vec = false; a.seed = seed;
+    a.iter = iter; a.ode_mask = ode_mask; a.lik_scale = lik_scale; a.eps = eps; a.minv = minv; a.tree = tree; a.ckpt = ckpt;
+    a.dst = dst; a.ist = ist; a.rank = rank; a.gnn = gnn; a.gode = gode; a.loss_sum = loss_sum; a.status = status; a.sd = sd;
+    return launch_nuts_post<R>((hipStream_t)stream, a);
+}
+
+template <typename R> int nuts_finish(void *stream, int C, int D, int ld, int adapt, double target_accept, R *z, R *g, double *U,
+                                      const R *tree, const double *dst, const int32_t *ist, double *log_eps, double *da, int n_ode,
+                                      const double *mu, const double *sd, R *draws, double *stats, int n_slots, int slot)
+{
+    if (!chains_ok(C, D, ld) || n_ode < 0 || n_ode > 17 || n_ode > D || (adapt != 0 && adapt != 1)) return HODE_EINVAL;
+    if (!(target_accept > 0.0 && target_accept < 1.0)) return HODE_EINVAL;
+    if (!z || !g || !U || !tree || !dst || !ist || !log_eps || !da) return HODE_EINVAL;
+    if (n_ode && (!mu || !sd)) return HODE_EINVAL;
+    if (slot >= 0 && (slot >= n_slots || !stats)) return HODE_EINVAL;
+    NutsFinishArgs<R> a;
+    a.C = C; a.D = D; a.ld = ld; a.adapt = adapt; a.n_ode = n_ode; a.n_slots = n_slots; a.slot = slot < 0 ? -1 : slot;
+    a.delta = target_accept; a.z = z; a.g = g; a.U = U; a.tree = tree; a.dst = dst; a.ist = ist; a.log_eps = log_eps; a.da = da;
+    a.mu = mu; a.sd = sd; a.draws = draws; a.stats = stats;
+    return launch_nuts_finish<R>((hipStream_t)stream, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -495,5 +553,41 @@ int hode_4gi_window_moments_f64(void *stream, const double *table, int ncols, in
     }
 HODE_HMC_ABI(f32, float)
 HODE_HMC_ABI(f64, double)
+
+#define HODE_NUTS_ABI(SFX, R)                                                                                                            \
+    int hode_nuts_begin_##SFX(void *stream, int C, int D, int ld, const R *z, const R *p, const R *g, const double *U,                \
+                              const double *U0, const double *ke0, R *tree, double *dst, int32_t *ist)                                \
+    {                                                                                                                                  \
+        return nuts_begin<R>(stream, C, D, ld, z, p, g, U, U0, ke0, tree, dst, ist);                                                  \
+    }                                                                                                                                  \
+    int hode_nuts_pre_##SFX(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, const double *eps, const R *minv,       \
+                            R *tree, int32_t *ist, const int32_t *rank, uint32_t ode_mask, const double *mu, const double *sd,        \
+                            int sample_nn, int P, R *nn_p, R *ode_p)                                                                  \
+    {                                                                                                                                  \
+        return nuts_pre<R>(stream, C, D, ld, seed, iter, eps, minv, tree, ist, rank, ode_mask, mu, sd, sample_nn, P, nn_p, ode_p);    \
+    }                                                                                                                                  \
+    int hode_nuts_post_##SFX(void *stream, int C, int D, int ld, int max_depth, uint64_t seed, uint32_t iter, const double *eps,      \
+                             const R *minv, R *tree, R *ckpt, double *dst, int32_t *ist, const int32_t *rank, const R *gnn,           \
+                             const R *gode, int P, const double *loss_sum, double lik_scale, const int32_t *status, int n_traj,      \
+                             uint32_t ode_mask, const double *sd, int sample_nn)                                                      \
+    {                                                                                                                                  \
+        return nuts_post<R>(stream, C, D, ld, max_depth, seed, iter, eps, minv, tree, ckpt, dst, ist, rank, gnn, gode, P, loss_sum,  \
+                            lik_scale, status, n_traj, ode_mask, sd, sample_nn);                                                      \
+    }                                                                                                                                  \
+    int hode_nuts_finish_##SFX(void *stream, int C, int D, int ld, int adapt, double target_accept, R *z, R *g, double *U,           \
+                               const R *tree, const double *dst, const int32_t *ist, double *log_eps, double *da, int n_ode,          \
+                               const double *mu, const double *sd, R *draws, double *stats, int n_slots, int slot)                    \
+    {                                                                                                                                  \
+        return nuts_finish<R>(stream, C, D, ld, adapt, target_accept, z, g, U, tree, dst, ist, log_eps, da, n_ode, mu, sd, draws,    \
+                              stats, n_slots, slot);                                                                                  \
+    }
+HODE_NUTS_ABI(f32, float)
+HODE_NUTS_ABI(f64, double)
+
+int hode_nuts_compact(void *stream, int C, const int32_t *ist, int32_t *rank, int32_t *count)
+{
+    if (C < 1 || !ist || !rank || !count) return HODE_EINVAL;
+    return launch_nuts_compact((hipStream_t)stream, C, ist, rank, count);
+}
 
 }  // extern "C"

@@ -7,78 +7,11 @@
 //
 // Coordinates (z): d < n_ode are the sampled mechanistic constants, in ascending ODE-index order (the set bits of ode_mask),
 // theta = mu + sd z; the next P coordinates (sample_nn) are the MLP weights themselves, theta = z.
-#include "hode_kernels.h"
+#include "hode_chains.h"
 #include "hode_philox.h"
 
 namespace hode {
 namespace {
-
-constexpr int kThreads = 256;
-
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ int block_or(int v, int *sh)
-{
-    v = __any(v != 0) ? 1 : 0;
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const int r = sh[0] | sh[1] | sh[2] | sh[3];
-    __syncthreads();
-    return r;
-}
-
-// four consecutive reals: one 16-byte access (fp32) / two (fp64) when `vec`, else up to `n` scalars (nothing past the row)
-template <typename R> __device__ __forceinline__ void ld4(const R *p, bool vec, int n, R (&o)[4])
-{
-    if (vec) {
-        if constexpr (sizeof(R) == 4) {
-            const float4 a = *reinterpret_cast<const float4 *>(p);
-            o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-        } else {
-            const double2 a = reinterpret_cast<const double2 *>(p)[0], b = reinterpret_cast<const double2 *>(p)[1];
-            o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
-        }
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = k < n ? p[k] : R(0);
-}
-
-template <typename R> __device__ __forceinline__ void st4(R *p, bool vec, int n, const R (&o)[4])
-{
-    if (vec) {
-        if constexpr (sizeof(R) == 4) {
-            *reinterpret_cast<float4 *>(p) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-            reinterpret_cast<double2 *>(p)[0] = make_double2(o[0], o[1]);
-            reinterpret_cast<double2 *>(p)[1] = make_double2(o[2], o[3]);
-        }
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k < n) p[k] = o[k];
-}
-
-// ODE index of sampled coordinate d (< n_ode): the d-th set bit of the mask
-__device__ __forceinline__ int ode_index(uint32_t mask, int d)
-{
-    for (int k = 0; k < 17; ++k)
-        if ((mask >> k) & 1u) {
-            if (d == 0) return k;
-            --d;
-        }
-    return 0;
-}
 
 // ---------------------------------------------------------------- per-set sum of squares + cotangent
 template <typename R, bool VEC>
@@ -292,15 +225,7 @@ __global__ __launch_bounds__(kThreads) void accept_kernel(int D, int ld, bool ve
             const double a = div ? 0.0 : (dH <= 0 ? 1.0 : exp(-dH));
             const double u = u01(hmc_rng(seed, (uint32_t)c, iter, kRngAccept, 0).x);
             keep = !div && u < a;
-            if (mode == HODE_HMC_ADAPT) {                    // dual averaging (Hoffman & Gelman 2014, Stan's constants)
-                const double t = st[3] + 1.0, eta = 1.0 / (t + 10.0);
-                st[2] = (1.0 - eta) * st[2] + eta * (delta - a);
-                const double le = st[0] - sqrt(t) / 0.05 * st[2];
-                const double w = pow(t, -0.75);
-                st[1] = w * le + (1.0 - w) * st[1];
-                st[3] = t;
-                log_eps[c] = le;
-            }
+            if (mode == HODE_HMC_ADAPT) dual_average(st, delta, a, &log_eps[c]);
             if (slot >= 0) {
                 double *s = stats + ((int64_t)c * n_slots + slot) * 4;
                 s[0] = a;
@@ -364,15 +289,6 @@ __global__ __launch_bounds__(64) void welford_kernel(int C, int D, int ld, int f
     wf[d] = n; wf[D + d] = m; wf[2 * D + d] = m2;
 }
 
-template <typename R> bool rows_vec(int ld, std::initializer_list<const void *> ptrs)
-{
-    if (ld % 4) return false;
-    for (const void *p : ptrs)
-        if (p && ((uintptr_t)p & 15)) return false;
-    return true;
-}
-
-inline int done() { return hipGetLastError() == hipSuccess ? HODE_OK : HODE_ELAUNCH; }
 
 }  // namespace
 

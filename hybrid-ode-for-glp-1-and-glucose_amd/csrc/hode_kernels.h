@@ -154,6 +154,56 @@ template <typename R> int launch_hmc_leapfrog(hipStream_t s, const HmcLeapfrogAr
 template <typename R> int launch_hmc_accept(hipStream_t s, const HmcAcceptArgs<R> &a);
 template <typename R> int launch_hmc_welford(hipStream_t s, int C, int D, int ld, int flags, const R *z, double *wf, R *minv);
 
+// ---- MCMC (hode_nuts.hip): the per-chain passes of multi-chain No-U-Turn sampling; tree [HODE_NUTS_ROWS][C][ld], see include/hode.h
+template <typename R> struct NutsPreArgs {
+    int C, D, ld, n_ode, sample_nn, P;
+    uint64_t seed;
+    uint32_t iter, ode_mask;
+    const double *eps;
+    const R *minv;
+    R *tree;
+    int32_t *ist;
+    const int32_t *rank;
+    const double *mu, *sd;
+    R *nn_p, *ode_p;
+};
+template <typename R> struct NutsPostArgs {
+    int C, D, ld, max_depth, n_ode, P, n_traj;
+    bool vec;
+    uint64_t seed;
+    uint32_t iter, ode_mask;
+    double lik_scale;
+    const double *eps;
+    const R *minv;
+    R *tree, *ckpt;
+    double *dst;
+    int32_t *ist;
+    const int32_t *rank;
+    const R *gnn, *gode;
+    const double *loss_sum;
+    const int32_t *status;
+    const double *sd;
+};
+template <typename R> struct NutsFinishArgs {
+    int C, D, ld, adapt, n_ode, n_slots, slot;
+    double delta;
+    R *z, *g;
+    double *U;
+    const R *tree;
+    const double *dst;
+    const int32_t *ist;
+    double *log_eps, *da;
+    const double *mu, *sd;
+    R *draws;
+    double *stats;
+};
+template <typename R> int launch_nuts_begin(hipStream_t s, int C, int D, int ld, const R *z, const R *p, const R *g, const double *U,
+                                            const double *U0, const double *ke0, R *tree, double *dst, int32_t *ist);
+template <typename R> int launch_nuts_pre(hipStream_t s, const NutsPreArgs<R> &a);
+template <typename R> int launch_nuts_post(hipStream_t s, NutsPostArgs<R> a);
+int launch_nuts_compact(hipStream_t s, int C, const int32_t *ist, int32_t *rank, int32_t *count);
+template <typename R> int launch_nuts_finish(hipStream_t s, const NutsFinishArgs<R> &a);
+
 // ---- data side (hode_datagen.hip) ----------------------------------------------------------------------------
 // 4GI model parameters, in the order of include/hode.h (HODE_4GI_NPAR)
 struct FourGIPar {

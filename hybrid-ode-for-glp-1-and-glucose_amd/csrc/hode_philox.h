@@ -1,4 +1,4 @@
-// hode_philox.h -- Philox4x32-10 (Salmon et al., SC'11) for the HMC sampler (hode_hmc.hip), host- and device-callable.
+// hode_philox.h -- Philox4x32-10 (Salmon et al., SC'11) for the samplers (hode_hmc.hip, hode_nuts.hip), host- and device-callable.
 //
 // Stream layout (include/hode.h, "MCMC"): key = (seed bits 0..31, chain), counter = (coordinate group, stream tag,
 // iteration, seed bits 32..63).  One call gives four 32-bit words: four coordinates' normals (two Box-Muller pairs), or one
@@ -17,8 +17,10 @@
 
 namespace hode {
 
-// stream tags (counter word 1)
+// stream tags (counter word 1); the last three are the No-U-Turn sampler's (hode_nuts.hip): the direction of doubling j
+// (group j), the multinomial choice of leaf n (group n, counted over the tree from 1), the merge of subtree j (group j)
 constexpr uint32_t kRngMomentum = 0, kRngAccept = 1, kRngJitter = 2, kRngInit = 3;
+constexpr uint32_t kRngNutsDir = 4, kRngNutsLeaf = 5, kRngNutsMerge = 6;
 
 struct Philox4 { uint32_t x, y, z, w; };
 

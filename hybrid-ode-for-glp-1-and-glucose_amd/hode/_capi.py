@@ -25,7 +25,9 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_solve_bwd_inputs_f32", "hode_solve_bwd_inputs_f64", "hode_rhs_bwd_inputs_f32", "hode_rhs_bwd_inputs_f64",
            "hode_mse_sets_f32", "hode_mse_sets_f64", "hode_hmc_refresh_f32", "hode_hmc_refresh_f64", "hode_hmc_leapfrog_f32",
            "hode_hmc_leapfrog_f64", "hode_hmc_accept_f32", "hode_hmc_accept_f64", "hode_hmc_welford_f32", "hode_hmc_welford_f64",
-           "hode_solve_jvp_f32", "hode_solve_jvp_f64"]
+           "hode_solve_jvp_f32", "hode_solve_jvp_f64",
+           "hode_nuts_begin_f32", "hode_nuts_begin_f64", "hode_nuts_pre_f32", "hode_nuts_pre_f64", "hode_nuts_post_f32",
+           "hode_nuts_post_f64", "hode_nuts_compact", "hode_nuts_finish_f32", "hode_nuts_finish_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -402,6 +404,41 @@ def hmc_accept(C_, D, ld, mode, seed, it, target_accept, z, z0, g, g0, U, U0, ke
 def hmc_welford(C_, D, ld, flags, z, wf, minv):
     _check(getattr(load(), f"hode_hmc_welford_{_sfx(minv.dtype)}")(
         _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(flags), _ptr(z), _ptr(wf), _ptr(minv)), "hode_hmc_welford")
+
+
+NUTS_ROWS, NUTS_MAX_DEPTH = 15, 30
+
+
+def nuts_begin(C_, D, ld, z, p, g, U, U0, ke0, tree, dst, ist):
+    _check(getattr(load(), f"hode_nuts_begin_{_sfx(z.dtype)}")(
+        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), _ptr(z), _ptr(p), _ptr(g), _ptr(U), _ptr(U0), _ptr(ke0), _ptr(tree), _ptr(dst),
+        _ptr(ist)), "hode_nuts_begin")
+
+
+def nuts_pre(C_, D, ld, seed, it, eps, minv, tree, ist, rank, ode_mask, mu, sd, sample_nn, P, nn_p, ode_p):
+    _check(getattr(load(), f"hode_nuts_pre_{_sfx(tree.dtype)}")(
+        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_uint64(seed), C.c_uint32(it), _ptr(eps), _ptr(minv), _ptr(tree), _ptr(ist),
+        _ptr(rank), C.c_uint32(ode_mask), _ptr(mu), _ptr(sd), C.c_int(int(sample_nn)), C.c_int(P), _ptr(nn_p), _ptr(ode_p)), "hode_nuts_pre")
+
+
+def nuts_post(C_, D, ld, max_depth, seed, it, eps, minv, tree, ckpt, dst, ist, rank, gnn, gode, P, loss_sum, lik_scale, status, n_traj,
+              ode_mask, sd, sample_nn):
+    _check(getattr(load(), f"hode_nuts_post_{_sfx(tree.dtype)}")(
+        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(max_depth), C.c_uint64(seed), C.c_uint32(it), _ptr(eps), _ptr(minv),
+        _ptr(tree), _ptr(ckpt), _ptr(dst), _ptr(ist), _ptr(rank), _ptr(gnn), _ptr(gode), C.c_int(P), _ptr(loss_sum), C.c_double(lik_scale),
+        _ptr(status), C.c_int(n_traj), C.c_uint32(ode_mask), _ptr(sd), C.c_int(int(sample_nn))), "hode_nuts_post")
+
+
+def nuts_compact(C_, ist, rank, count):
+    _check(load().hode_nuts_compact(_stream(), C.c_int(C_), _ptr(ist), _ptr(rank), _ptr(count)), "hode_nuts_compact")
+
+
+def nuts_finish(C_, D, ld, adapt, target_accept, z, g, U, tree, dst, ist, log_eps, da, n_ode, mu, sd, draws=None, stats=None, n_slots=0,
+                slot=-1):
+    _check(getattr(load(), f"hode_nuts_finish_{_sfx(z.dtype)}")(
+        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(int(adapt)), C.c_double(target_accept), _ptr(z), _ptr(g), _ptr(U),
+        _ptr(tree), _ptr(dst), _ptr(ist), _ptr(log_eps), _ptr(da), C.c_int(n_ode), _ptr(mu), _ptr(sd), _ptr(draws), _ptr(stats),
+        C.c_int(n_slots), C.c_int(slot)), "hode_nuts_finish")
 
 
 # --------------------------------------------------------------------------------------------- data side

@@ -119,13 +119,14 @@ class _Sampler:
         self.gnn = self.gode = None
 
     # ------------------------------------------------------------------ the pieces of an iteration
-    def evaluate(self):
-        """Likelihood sum of squares, its gradient and the solve statuses at the parameters in nn_p / ode_p (all chains):
-        forward with tape -> hode_mse_sets -> adjoint, cut into tape-budget pieces the way _gauss_lik_core cuts them."""
+    def evaluate(self, n_sets=None):
+        """Likelihood sum of squares, its gradient and the solve statuses at the parameters in nn_p / ode_p: of all chains, or
+        of the first n_sets parameter sets (the NUTS driver's compacted active chains); forward with tape -> hode_mse_sets ->
+        adjoint, cut into tape-budget pieces the way _gauss_lik_core cuts them."""
         if not self.has_data:
             return
         from models.hybrid_ode_nn import _pieces, _small_tape_steps, _solve_taped, _tape_budget, _tape_steps
-        C, N, T, P = self.C, self.N, self.T, self.P
+        C, N, T, P = self.C if n_sets is None else int(n_sets), self.N, self.T, self.P
         elem = self.x0.element_size()
         ts = self.model.tape_steps
         steps = _small_tape_steps(C * N, T, self.method, elem, self.L, self.H, ts) or _tape_steps(T, self.method, ts)
@@ -138,6 +139,8 @@ class _Sampler:
         if not one:
             self.gnn = torch.zeros(C * P, dtype=self.dt, device=self.dev) if want_nn else None
             self.gode = torch.zeros(C * 17, dtype=self.dt, device=self.dev) if want_ode else None
+            if self.status.shape[0] < C:                # a smaller one-piece evaluation left a view of its own statuses
+                self.status = torch.zeros(self.C, N, dtype=torch.int32, device=self.dev)
         tape = None
         for s0, s1, lo, hi in pieces:
             m = s1 - s0

@@ -389,6 +389,66 @@ int hode_hmc_accept_f64(void *stream, int C, int D, int ld, int mode, uint64_t s
 int hode_hmc_welford_f32(void *stream, int C, int D, int ld, int flags, const float *z, double *wf, float *minv);
 int hode_hmc_welford_f64(void *stream, int C, int D, int ld, int flags, const double *z, double *wf, double *minv);
 
+/* ---- No-U-Turn sampling (inference/nuts.py, run_nuts): multinomial NUTS with the generalised U-turn criterion, every
+ *      chain's tree built one leaf per global step.  An iteration is hode_hmc_refresh, hode_nuts_begin, hode_nuts_compact,
+ *      then, while the count of active chains A > 0: hode_nuts_pre, the solve + hode_mse_sets + adjoint of the A active
+ *      chains' parameter sets, hode_nuts_post, hode_nuts_compact; then hode_nuts_finish.  Chains, coordinates, mu / sd and
+ *      minv as for the HMC passes above.
+ *   - tree: [HODE_NUTS_ROWS][C][ld] reals, rows {frontier z, p, g; left edge z, p, g; right edge z, p, g; proposal z, g;
+ *     subtree proposal z, g; rho; rho_sub}; ckpt: [C][max_depth][2][ld] reals (the open U-turn blocks' first p# and the
+ *     momentum sum before it); dst: fp64 [C][8] {H0, log_w, log_w_sub, sum_acc, U of the proposal, U of the subtree
+ *     proposal}; ist: int32 [C][8] {j, leaf in the subtree, n_leaf, active, divergent, failed, direction, tree_depth};
+ *   - rank: int32 [C], the chain's slot in the compacted solve (hode_nuts_compact: active chains numbered 0..A-1 in chain
+ *     order, -1 for the others); count: int32 [1], A;
+ *   - random numbers: Philox streams 4 (direction of doubling j, group j), 5 (multinomial choice of leaf n, group n) and 6
+ *     (merge of subtree j, group j) of the chain and `iter`: independent of C and of the slot. */
+#define HODE_NUTS_ROWS 15
+#define HODE_NUTS_MAX_DEPTH 30
+
+/* tree set-up after hode_hmc_refresh: edges and frontier = (z, p, g), proposal = (z, g, U), rho = p, H0 = U0 + ke0, log_w = 0,
+ * j = n_leaf = 0, every chain active. */
+int hode_nuts_begin_f32(void *stream, int C, int D, int ld, const float *z, const float *p, const float *g, const double *U,
+                        const double *U0, const double *ke0, float *tree, double *dst, int32_t *ist);
+int hode_nuts_begin_f64(void *stream, int C, int D, int ld, const double *z, const double *p, const double *g, const double *U,
+                        const double *U0, const double *ke0, double *tree, double *dst, int32_t *ist);
+
+/* start of a leaf of every active chain: at a doubling's first leaf its direction v (stream 4) and frontier = the edge on side
+ * v; then p -= v eps/2 g, z += v eps minv p at the frontier, and the sampled entries of nn_p[rank][P] / ode_p[rank][17] (NULL:
+ * not written) from z. */
+int hode_nuts_pre_f32(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, const double *eps, const float *minv,
+                      float *tree, int32_t *ist, const int32_t *rank, uint32_t ode_mask, const double *mu, const double *sd,
+                      int sample_nn, int P, float *nn_p, float *ode_p);
+int hode_nuts_pre_f64(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, const double *eps, const double *minv,
+                      double *tree, int32_t *ist, const int32_t *rank, uint32_t ode_mask, const double *mu, const double *sd,
+                      int sample_nn, int P, double *nn_p, double *ode_p);
+
+/* end of a leaf of every active chain: grad U and U from slot rank[c] of gnn[A][P] / gode[A][17] / loss_sum[A] / status[A][n_traj]
+ * (as hode_hmc_leapfrog's HODE_HMC_ASSEMBLE; NULL: no likelihood term), p -= v eps/2 g, H = U + ke; then divergence (failed
+ * solve, H not finite, H - H0 > 1000), the accept statistic, the multinomial choice inside the subtree (stream 5), rho_sub,
+ * the U-turn checks of the aligned blocks that end here, and, when the subtree is complete, the biased progressive choice
+ * (stream 6), the merge and the U-turn check of the whole tree.  A divergence, a U-turn or j = max_depth ends the chain's tree. */
+int hode_nuts_post_f32(void *stream, int C, int D, int ld, int max_depth, uint64_t seed, uint32_t iter, const double *eps,
+                       const float *minv, float *tree, float *ckpt, double *dst, int32_t *ist, const int32_t *rank,
+                       const float *gnn, const float *gode, int P, const double *loss_sum, double lik_scale,
+                       const int32_t *status, int n_traj, uint32_t ode_mask, const double *sd, int sample_nn);
+int hode_nuts_post_f64(void *stream, int C, int D, int ld, int max_depth, uint64_t seed, uint32_t iter, const double *eps,
+                       const double *minv, double *tree, double *ckpt, double *dst, int32_t *ist, const int32_t *rank,
+                       const double *gnn, const double *gode, int P, const double *loss_sum, double lik_scale,
+                       const int32_t *status, int n_traj, uint32_t ode_mask, const double *sd, int sample_nn);
+
+/* active flags -> rank[C] and count[0] = A (one workgroup, chains in order). */
+int hode_nuts_compact(void *stream, int C, const int32_t *ist, int32_t *rank, int32_t *count);
+
+/* end of an iteration: (z, g, U) = the tree's proposal; accept statistic = sum_acc / n_leaf; adapt = 1: one dual-averaging
+ * update of log_eps with it (da as for hode_hmc_accept); slot >= 0 stores draws[C][n_slots][D] (natural coordinates, may be
+ * NULL) and stats[C][n_slots][6] = {accept statistic, log posterior (-U), divergent, failed solve, tree_depth, n_leapfrog}. */
+int hode_nuts_finish_f32(void *stream, int C, int D, int ld, int adapt, double target_accept, float *z, float *g, double *U,
+                         const float *tree, const double *dst, const int32_t *ist, double *log_eps, double *da, int n_ode,
+                         const double *mu, const double *sd, float *draws, double *stats, int n_slots, int slot);
+int hode_nuts_finish_f64(void *stream, int C, int D, int ld, int adapt, double target_accept, double *z, double *g, double *U,
+                         const double *tree, const double *dst, const int32_t *ist, double *log_eps, double *da, int n_ode,
+                         const double *mu, const double *sd, double *draws, double *stats, int n_slots, int slot);
+
 #ifdef __cplusplus
 }
 #endif
