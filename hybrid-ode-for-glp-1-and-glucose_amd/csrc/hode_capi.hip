@@ -164,6 +164,23 @@ template <typename R> int mse_sets(void *stream, int n_sets, int64_t len, const 
     return launch_mse_sets<R>((hipStream_t)stream, n_sets, len, y, obs, scale, loss_sum, gy);
 }
 
+template <typename R> int obs_nll_sets(void *stream, int n_sets, int64_t len, const R *y, const R *obs, const uint8_t *mask, int mode, int flags,
+                                       const double *w, const double *a, const double *b, const double *n, double *sse, double *loss_sum, R *gy)
+{
+    if (n_sets < 0 || len < 0 || (mode != HODE_OBS_FIXED && mode != HODE_OBS_MARGINAL) || flags < 0 || flags > HODE_OBS_FROM_SSE)
+        return HODE_EINVAL;
+    if (mode == HODE_OBS_FIXED ? !w : (!a || !b || !n)) return HODE_EINVAL;
+    for (int k = 0; k < 6; ++k) {
+        if (mode == HODE_OBS_FIXED ? !(w[k] > 0.0) : (!(a[k] > 0.0) || !(b[k] > 0.0) || !(n[k] >= 0.0))) return HODE_EINVAL;
+    }
+    if (n_sets == 0 || len == 0) return HODE_OK;
+    if (!y || !obs || !sse) return HODE_EINVAL;
+    ObsArgs<R> o{};
+    o.n_sets = n_sets; o.mode = mode; o.flags = flags; o.len = len; o.y = y; o.obs = obs; o.mask = mask;
+    o.w = w; o.a = a; o.b = b; o.n = n; o.sse = sse; o.loss_sum = loss_sum; o.gy = gy;
+    return launch_obs_nll_sets<R>((hipStream_t)stream, o);
+}
+
 template <typename R> int hmc_refresh(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, double jitter, const R *minv,
                                       const double *log_eps, const R *z, const R *g, const double *U, R *p, R *z0, R *g0, double *U0,
                                       double *ke0, double *eps, int32_t *failed)
@@ -551,6 +568,16 @@ int hode_4gi_window_moments_f64(void *stream, const double *table, int ncols, in
     {                                                                                                                                  \
         return hmc_welford<R>(stream, C, D, ld, flags, z, wf, minv);                                                                  \
     }
+#define HODE_OBS_ABI(SFX, R)                                                                                                             \
+    int hode_obs_nll_sets_##SFX(void *stream, int n_sets, int64_t len, const R *y, const R *obs, const uint8_t *mask, int mode,        \
+                                int flags, const double *w, const double *a, const double *b, const double *n, double *sse,           \
+                                double *loss_sum, R *gy)                                                                              \
+    {                                                                                                                                  \
+        return obs_nll_sets<R>(stream, n_sets, len, y, obs, mask, mode, flags, w, a, b, n, sse, loss_sum, gy);                       \
+    }
+HODE_OBS_ABI(f32, float)
+HODE_OBS_ABI(f64, double)
+
 HODE_HMC_ABI(f32, float)
 HODE_HMC_ABI(f64, double)
 

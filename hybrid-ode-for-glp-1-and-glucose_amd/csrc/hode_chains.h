@@ -38,6 +38,24 @@ __device__ __forceinline__ void block_sum2(double &a, double &b, double *sh)
     __syncthreads();
 }
 
+// six chain sums at once (sh: 24 doubles), each in the order of block_sum: the per-state sums of hode_obs.hip
+__device__ __forceinline__ void block_sum6(double (&v)[6], double *sh)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v[k] += __shfl_xor(v[k], o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) sh[4 * k + (threadIdx.x >> 6)] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = (sh[4 * k] + sh[4 * k + 1]) + (sh[4 * k + 2] + sh[4 * k + 3]);
+    __syncthreads();
+}
+
 __device__ __forceinline__ int block_or(int v, int *sh)
 {
     v = __any(v != 0) ? 1 : 0;

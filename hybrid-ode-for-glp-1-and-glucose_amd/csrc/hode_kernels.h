@@ -103,6 +103,17 @@ int launch_selftest(hipStream_t s, int32_t *out);
 
 // ---- MCMC (hode_hmc.hip): the per-chain passes of multi-chain HMC; chains [C][ld] row-major, see include/hode.h
 template <typename R> int launch_mse_sets(hipStream_t s, int n_sets, int64_t len, const R *y, const R *obs, R scale, double *loss_sum, R *gy);
+// the observation model (hode_obs.hip); w / a / b / n are HOST arrays of six
+template <typename R> struct ObsArgs {
+    int n_sets, mode, flags;
+    int64_t len;
+    const R *y, *obs;
+    const uint8_t *mask;
+    const double *w, *a, *b, *n;
+    double *sse, *loss_sum;
+    R *gy;
+};
+template <typename R> int launch_obs_nll_sets(hipStream_t s, const ObsArgs<R> &a);
 template <typename R> struct HmcRefreshArgs {
     int C, D, ld;
     uint64_t seed;

@@ -27,7 +27,8 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_hmc_leapfrog_f64", "hode_hmc_accept_f32", "hode_hmc_accept_f64", "hode_hmc_welford_f32", "hode_hmc_welford_f64",
            "hode_solve_jvp_f32", "hode_solve_jvp_f64",
            "hode_nuts_begin_f32", "hode_nuts_begin_f64", "hode_nuts_pre_f32", "hode_nuts_pre_f64", "hode_nuts_post_f32",
-           "hode_nuts_post_f64", "hode_nuts_compact", "hode_nuts_finish_f32", "hode_nuts_finish_f64"]
+           "hode_nuts_post_f64", "hode_nuts_compact", "hode_nuts_finish_f32", "hode_nuts_finish_f64",
+           "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -374,6 +375,38 @@ def mse_sets(y, obs, scale, loss_sum, want_grad=True):
     gy = torch.empty_like(y) if want_grad else None
     _check(getattr(load(), f"hode_mse_sets_{_sfx(y.dtype)}")(_stream(), C.c_int(n_sets), C.c_int64(obs.numel()), _ptr(y), _ptr(obs),
                                                            _real(y.dtype)(scale), _ptr(loss_sum), _ptr(gy)), "hode_mse_sets")
+    return gy
+
+
+OBS_FIXED, OBS_MARGINAL = 0, 1
+OBS_SUMS_ONLY, OBS_FROM_SSE = 1, 2
+
+
+def _six(v):
+    return None if v is None else (C.c_double * 6)(*[float(x) for x in v])
+
+
+def obs_nll_sets(y, obs, mask, mode, sse, loss_sum=None, w=None, a=None, b=None, n=None, flags=0, want_grad=True):
+    """The observation model's negative log-likelihood per set (include/hode.h "Observation model"): y[n_sets, ...] against ONE
+    obs shared by every set; mask uint8 like obs or None; mode OBS_FIXED (w = 1/sigma^2 per state) or OBS_MARGINAL (a, b, n per
+    state), six host floats each; sse fp64[n_sets, 6] and loss_sum fp64[n_sets] (or None) ACCUMULATED; flags 0 / OBS_SUMS_ONLY /
+    OBS_FROM_SSE.  Returns gy (None with want_grad=False or OBS_SUMS_ONLY)."""
+    _need_gpu(y)
+    y = y.contiguous()
+    n_sets = y.shape[0]
+    obs = obs.to(device=y.device, dtype=y.dtype).contiguous()
+    if y.numel() != n_sets * obs.numel() or sse.dtype != torch.float64 or sse.numel() < 6 * n_sets or not sse.is_contiguous():
+        raise HodeError("obs_nll_sets: y must be [n_sets, len(obs)] and sse fp64[n_sets, 6]")
+    if loss_sum is not None and (loss_sum.dtype != torch.float64 or loss_sum.numel() < n_sets):
+        raise HodeError("obs_nll_sets: loss_sum must be fp64[n_sets]")
+    if mask is not None:
+        mask = mask.to(device=y.device).contiguous()
+        if mask.dtype != torch.uint8 or mask.numel() != obs.numel():
+            raise HodeError("obs_nll_sets: mask must be uint8 with the shape of obs")
+    gy = torch.empty_like(y) if want_grad and flags != OBS_SUMS_ONLY else None
+    _check(getattr(load(), f"hode_obs_nll_sets_{_sfx(y.dtype)}")(_stream(), C.c_int(n_sets), C.c_int64(obs.numel()), _ptr(y), _ptr(obs),
+                                                               _ptr(mask), C.c_int(mode), C.c_int(flags), _six(w), _six(a), _six(b),
+                                                               _six(n), _ptr(sse), _ptr(loss_sum), _ptr(gy)), "hode_obs_nll_sets")
     return gy
 
 

@@ -1,8 +1,9 @@
 """Multi-chain Hamiltonian Monte Carlo over a HybridODENN on the GPU: `run_hmc`, the replacement for the reference's
 `run_nuts` (inference/mcmc.py:17-173, a one-chain random-walk placeholder that samples its prior).
 
-Target (the density run_nuts intends, mcmc.py:50-98): a Gaussian likelihood with fixed noise_sigma over one batch dict
-{initial_state, observations, time_points, external_inputs}; Gaussian priors on the sampled mechanistic constants (the
+Target (the density run_nuts intends, mcmc.py:50-98): a Gaussian likelihood over one batch dict {initial_state, observations,
+time_points, external_inputs[, observation_mask]} -- noise_sigma fixed (a scalar or one value per state) or, noise="marginal",
+inferred (inference/observation.py; NaN or masked observations are missing); Gaussian priors on the sampled mechanistic constants (the
 reference's seven by default) and N(0, 1) on every MLP weight.  The chains move in prior-standardised coordinates z
 (theta_ode = mu + sd z, theta_nn = z), so the identity is a sensible first mass matrix.
 
@@ -54,9 +55,11 @@ class _Sampler:
     directly; run_hmc is the schedule around it."""
 
     def __init__(self, model, data, n_chains, noise_sigma=1.0, ode_priors=None, sample_nn=True, seed=0, solver="dopri5",
-                 rtol=1e-6, atol=1e-8, dtype=torch.float32, jitter=0.1):
+                 rtol=1e-6, atol=1e-8, dtype=torch.float32, jitter=0.1, noise="fixed", noise_prior=None):
+        from inference.observation import ObservationModel
         from models.hybrid_ode_nn import _SOLVERS, _compute_device
         from models.ode_core import ODE_PARAM_NAMES
+        self.om = ObservationModel(noise_sigma, noise, noise_prior)          # validates before any device is needed
         model._check_supported()
         self.model, self.dt = model, dtype
         dev = self.dev = _compute_device()
@@ -103,8 +106,9 @@ class _Sampler:
         self.search = torch.zeros(C, 2, dtype=torch.int32, device=dev)
         self.failed = torch.zeros(C, dtype=torch.int32, device=dev)
         self.wf = torch.zeros(3, self.D, **f64)
-        self.lik_scale = 0.5 / float(noise_sigma) ** 2
+        self.lik_scale = 0.5 / float(self.om.sigma[0]) ** 2
         self.loss_sum = torch.zeros(C, **f64)
+        self.obs_kernel = False
         self.has_data = data is not None
         if self.has_data:
             x0, t, ins = model._prep_inputs(data["initial_state"], data["time_points"], data.get("external_inputs"), dev)
@@ -112,17 +116,25 @@ class _Sampler:
             self.x0, self.t = cast(x0), cast(t)
             self.meal, self.tvns, self.gd = cast(ins["meal"]), cast(ins["tVNS"]), cast(ins["GD"])
             self.N, self.T = self.x0.shape[0], self.t.shape[-1]
-            self.obs = data["observations"].to(dev, dtype).reshape(self.N, -1).contiguous()
-            if self.obs.shape[1] != self.T * 6:
+            if tuple(data["observations"].shape) != (self.N, self.T, 6):
                 raise ValueError("observations must be [B, T, 6] on the grid of time_points")
+            self.om.prepare(data["observations"], data.get("observation_mask"), dev, dtype)
+            self.obs = self.om.obs
+            # missing entries, per-state sigma or inferred noise: the observation kernel gives the negative log-likelihood itself
+            # (lik_scale = 1).  Complete data with one fixed sigma stay on hode_mse_sets, bit for bit.
+            self.obs_kernel = self.om.needs_kernel
+            if self.obs_kernel:
+                self.lik_scale = 1.0
+                self.sse = torch.zeros(C, 6, **f64)
             self.status = torch.zeros(C, self.N, dtype=torch.int32, device=dev)
         self.gnn = self.gode = None
 
     # ------------------------------------------------------------------ the pieces of an iteration
     def evaluate(self, n_sets=None):
         """Likelihood sum of squares, its gradient and the solve statuses at the parameters in nn_p / ode_p: of all chains, or
-        of the first n_sets parameter sets (the NUTS driver's compacted active chains); forward with tape -> hode_mse_sets ->
-        adjoint, cut into tape-budget pieces the way _gauss_lik_core cuts them."""
+        of the first n_sets parameter sets (the NUTS driver's compacted active chains); forward with tape -> hode_mse_sets (or
+        hode_obs_nll_sets: the negative log-likelihood of the observation model) -> adjoint, cut into tape-budget pieces the way
+        _gauss_lik_core cuts them."""
         if not self.has_data:
             return
         from models.hybrid_ode_nn import _pieces, _small_tape_steps, _solve_taped, _tape_budget, _tape_steps
@@ -141,6 +153,18 @@ class _Sampler:
             self.gode = torch.zeros(C * 17, dtype=self.dt, device=self.dev) if want_ode else None
             if self.status.shape[0] < C:                # a smaller one-piece evaluation left a view of its own statuses
                 self.status = torch.zeros(self.C, N, dtype=torch.int32, device=self.dev)
+        flags = 0
+        if self.obs_kernel:
+            self.sse.zero_()
+            if self.om.marginal and pieces[0][3] - pieces[0][2] < N:
+                # a set cut into pieces: its cotangent needs the sums of the WHOLE set, so the pieces run once without a tape first
+                flags = hode.capi.OBS_FROM_SSE
+                for s0, s1, lo, hi in pieces:
+                    cut = lambda v: None if v is None else v[lo:hi]              # noqa: E731
+                    y = hode.solve_fwd(self.x0[lo:hi], self.t if self.t.dim() == 1 else self.t[lo:hi], cut(self.meal), cut(self.tvns),
+                                       cut(self.gd), self.ode_p[17 * s0:17 * s1], self.nn_p[P * s0:P * s1], self.H, self.L,
+                                       method=self.method, rtol=self.rtol, atol=self.atol, n_sets=1).y
+                    self.om.nll_sets(y.view(1, -1), None, self.sse[s0:s1], lo, hi, hode.capi.OBS_SUMS_ONLY)
         tape = None
         for s0, s1, lo, hi in pieces:
             m = s1 - s0
@@ -149,7 +173,11 @@ class _Sampler:
                                self.ode_p[17 * s0:17 * s1], self.nn_p[P * s0:P * s1], self.H, self.L, self.method, self.rtol,
                                self.atol, m, steps, tape=tape)
             tape = sol.tape
-            gy = hode.capi.mse_sets(sol.y.view(m, -1), self.obs[lo:hi], self.lik_scale, self.loss_sum[s0:s1])
+            if self.obs_kernel:
+                ls = self.loss_sum[s0:s1] if flags == 0 or lo == 0 else None           # the finished sums' nll: once per set
+                gy = self.om.nll_sets(sol.y.view(m, -1), ls, self.sse[s0:s1], lo, hi, flags)
+            else:
+                gy = hode.capi.mse_sets(sol.y.view(m, -1), self.obs[lo:hi], self.lik_scale, self.loss_sum[s0:s1])
             _, gn, go = sol.backward(gy.view_as(sol.y), want_gnn=want_nn, want_gode=want_ode)
             if one:
                 self.gnn, self.gode = gn, go
@@ -269,13 +297,15 @@ class HMCResult:
     """Draws of run_hmc.  `samples`: numpy arrays keyed like the reference's draws (`ode.<name>`, `nn.<parameter name>`),
     shaped [chains, draws, ...]; `flat()`: the same as [chains * draws, ...] (what reference posterior_summary takes);
     `stats`: accept_prob / log_posterior / divergent / failed_solve [chains, draws], step_size [chains], inv_mass [D];
-    `rhat()` / `ess()`: split R-hat and multi-chain bulk ESS of every coordinate; `predict(...)`: posterior predictive."""
+    `rhat()` / `ess()`: split R-hat and multi-chain bulk ESS of every coordinate; `predict(...)`: posterior predictive;
+    `noise_sigma(...)`: draws of the observation noise (inferred with noise="marginal", else the fixed values)."""
 
-    def __init__(self, draws, ode_names, nn_names, stats, model=None, ode_base=None, nn_base=None):
+    def __init__(self, draws, ode_names, nn_names, stats, model=None, ode_base=None, nn_base=None, observation=None, data=None):
         self.draws = draws                          # [C, n, D] natural coordinates (device or CPU tensor)
         self.ode_names, self.nn_names = list(ode_names), list(nn_names)
         self.stats = stats
         self.model, self.ode_base, self.nn_base = model, ode_base, nn_base
+        self.observation, self.data = observation, data      # the run's ObservationModel and batch (noise_sigma's defaults)
         self._samples = None
 
     @property
@@ -329,8 +359,43 @@ class HMCResult:
         nn = d[:, n_ode:n_ode + P] if d.shape[1] >= n_ode + P else self.nn_base.to(d.device, torch.float32).reshape(1, P).repeat(S, 1)
         return S, nn.contiguous().reshape(-1), ode.reshape(-1).contiguous()
 
-    def predict(self, initial_state, t_span, external_inputs=None, thin=1, solver="dopri5", rtol=1e-6, atol=1e-8):
-        """Posterior predictive of the kept draws (every `thin`-th of each chain), ONE batched solve -> [n_draws, B, T, 6]."""
+    def noise_sigma(self, data=None, thin=1, seed=0, solver="dopri5", rtol=1e-6, atol=1e-8):
+        """Draws of the per-state observation noise sigma, [n_draws, 6] (fp64, on the compute device), one per kept draw (every
+        `thin`-th of each chain).  noise="marginal": sigma_k^2 | theta, obs is inverse-gamma, drawn exactly from the sums of
+        squares of the kept draws against `data` (default: the run's batch) -- ONE batched solve, the observation kernel in
+        its sums-only mode, then `ObservationModel.sample_noise`; a state observed nowhere is drawn from its prior.
+        noise="fixed": the fixed values repeated."""
+        from inference.observation import ObservationModel
+        from models.hybrid_ode_nn import _compute_device
+        om = self.observation if self.observation is not None else ObservationModel()
+        dev = _compute_device()
+        S = self.draws[:, ::thin].shape[0] * self.draws[:, ::thin].shape[1]
+        sse = torch.zeros(S, 6, dtype=torch.float64, device=dev)
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        if not om.marginal:
+            return om.sample_noise(sse)
+        data = self.data if data is None else data
+        if data is None:
+            raise ValueError("noise_sigma needs the batch the noise is inferred from")
+        y = self._solve_draws(data["initial_state"], data["time_points"], data.get("external_inputs"), thin, solver, rtol, atol)
+        bound = ObservationModel(om.sigma, om.noise, (om.a, om.b)).prepare(data["observations"], data.get("observation_mask"), dev,
+                                                                             y.dtype)
+        bound.nll_sets(y.reshape(S, -1), None, sse, flags=hode.capi.OBS_SUMS_ONLY)
+        return bound.sample_noise(sse, gen)
+
+    def predict(self, initial_state, t_span, external_inputs=None, thin=1, solver="dopri5", rtol=1e-6, atol=1e-8,
+                observation_noise=False, data=None, seed=0):
+        """Posterior predictive of the kept draws (every `thin`-th of each chain), ONE batched solve -> [n_draws, B, T, 6].
+        observation_noise=True adds N(0, sigma_k^2) to every entry with the draws of `noise_sigma(data, thin, seed)`."""
+        y = self._solve_draws(initial_state, t_span, external_inputs, thin, solver, rtol, atol)
+        if observation_noise:
+            sig = self.noise_sigma(data, thin, seed, solver, rtol, atol).to(y.dtype)
+            gen = torch.Generator(device=y.device).manual_seed(int(seed) + 1)
+            y = y + sig.view(-1, 1, 1, 6) * torch.randn(y.shape, dtype=y.dtype, device=y.device, generator=gen)
+        return y.to(self.model.device)
+
+    def _solve_draws(self, initial_state, t_span, external_inputs, thin, solver, rtol, atol):
+        """[n_draws, B, T, 6] on the compute device."""
         if self.model is None:
             raise ValueError("this result carries no model (built from arrays)")
         m = self.model
@@ -347,7 +412,7 @@ class HMCResult:
             y = m._solve(x0.repeat(S, 1), rep(t) if t.dim() == 2 else t, u, solver, rtol, atol, n_sets=S, nn_flat=nn_flat,
                          ode_vec=ode_vec, differentiable=False)
         m._warn_failures(m.last_solve_info)
-        return y.reshape(S, B, y.shape[1], 6).to(m.device)
+        return y.reshape(S, B, y.shape[1], 6)
 
 
 # ---------------------------------------------------------------------------------------------------- entry point
@@ -355,8 +420,13 @@ def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1
             n_leapfrog: int = 16, target_accept: float = 0.8, noise_sigma: float = 1.0,
             ode_priors: Optional[Dict[str, Tuple[float, float]]] = None, sample_nn: bool = True, thin: int = 1, seed: int = 0,
             solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8, device=None, dtype=torch.float32,
-            jitter: float = 0.1, progress=None) -> HMCResult:
+            jitter: float = 0.1, progress=None, noise: str = "fixed", noise_prior=None) -> HMCResult:
     """Sample the posterior of `model` given the batch `data` (None: the prior alone) with n_chains chains.
+
+    Observations that are NaN, or false in data["observation_mask"] (bool [B, T, 6]), are missing; a state may be observed
+    nowhere.  noise_sigma: a scalar or one value per state.  noise="marginal" infers the noise instead: sigma_k^2 ~
+    InvGamma(a_k, b_k) is integrated out (default a_k = 2, b_k = noise_sigma_k^2; noise_prior=(a, b) overrides) and the result's
+    `noise_sigma()` draws it back (inference/observation.py).
 
     num_warmup iterations adapt the per-chain step size (dual averaging to target_accept) and the pooled diagonal mass matrix
     (Stan's windows); then num_samples iterations, every `thin`-th kept.  ode_priors: name -> (mean, std) of the sampled
@@ -367,7 +437,7 @@ def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1
         raise ValueError("num_samples, n_chains, n_leapfrog, thin must be >= 1 and num_warmup >= 0")
     if not 0.0 < target_accept < 1.0:
         raise ValueError("target_accept must lie in (0, 1)")
-    s = _Sampler(model, data, n_chains, noise_sigma, ode_priors, sample_nn, seed, solver, rtol, atol, dtype, jitter)
+    s = _Sampler(model, data, n_chains, noise_sigma, ode_priors, sample_nn, seed, solver, rtol, atol, dtype, jitter, noise, noise_prior)
     C, D = s.C, s.D
     n_slots = (num_samples + thin - 1) // thin
     draws = torch.empty(C, n_slots, D, dtype=dtype, device=s.dev)
@@ -400,4 +470,4 @@ def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1
     st = {"accept_prob": stats[..., 0].cpu().numpy(), "log_posterior": stats[..., 1].cpu().numpy(),
           "divergent": stats[..., 2].cpu().numpy() > 0, "failed_solve": stats[..., 3].cpu().numpy() > 0,
           "step_size": s.log_eps.exp().cpu().numpy(), "inv_mass": s.minv[:D].double().cpu().numpy()}
-    return HMCResult(draws, s.ode_names, s.nn_names if sample_nn else [], st, model, s.ode_base, s.nn_base)
+    return HMCResult(draws, s.ode_names, s.nn_names if sample_nn else [], st, model, s.ode_base, s.nn_base, s.om, data)

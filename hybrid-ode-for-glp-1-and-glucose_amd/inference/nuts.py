@@ -69,10 +69,11 @@ def run_nuts(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 
              target_accept: float = 0.8, max_tree_depth: int = 10, device=None, *, n_chains: int = 64, noise_sigma: float = 1.0,
              ode_priors: Optional[Dict[str, Tuple[float, float]]] = None, sample_nn: bool = True, thin: int = 1, seed: int = 0,
              solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8, dtype=torch.float32, jitter: float = 0.1,
-             progress=None) -> HMCResult:
+             progress=None, noise: str = "fixed", noise_prior=None) -> HMCResult:
     """Sample the posterior of `model` given the batch `data` (None: the prior alone) with n_chains chains of NUTS.
 
-    The target, priors and warm-up are run_hmc's: num_warmup iterations adapt the per-chain step size (dual averaging of the
+    The target, priors, observation model (missing observations, noise_sigma per state, noise="marginal" / noise_prior) and
+    warm-up are run_hmc's: num_warmup iterations adapt the per-chain step size (dual averaging of the
     tree's accept statistic to target_accept) and the pooled diagonal mass matrix (Stan's windows); then num_samples
     iterations, every `thin`-th kept.  Each tree doubles at most max_tree_depth times.  `device` is accepted for the
     reference's signature: the work runs on the HIP device.  `progress(it, stats)`, if given, is called once per iteration.
@@ -84,7 +85,7 @@ def run_nuts(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 
     if not 0.0 < target_accept < 1.0:
         raise ValueError("target_accept must lie in (0, 1)")
     s = _NutsSampler(model, data, n_chains, max_tree_depth, noise_sigma=noise_sigma, ode_priors=ode_priors, sample_nn=sample_nn,
-                     seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter)
+                     seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter, noise=noise, noise_prior=noise_prior)
     C, D = s.C, s.D
     n_slots = (num_samples + thin - 1) // thin
     draws = torch.empty(C, n_slots, D, dtype=dtype, device=s.dev)
@@ -120,4 +121,4 @@ def run_nuts(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 
            "tree_depth": st[..., 4].astype(np.int64), "n_leapfrog": st[..., 5].astype(np.int64),
            "step_size": s.log_eps.exp().cpu().numpy(), "inv_mass": s.minv[:D].double().cpu().numpy(),
            "trajectories_solved": np.asarray(solved, dtype=np.int64)}
-    return HMCResult(draws, s.ode_names, s.nn_names if sample_nn else [], out, model, s.ode_base, s.nn_base)
+    return HMCResult(draws, s.ode_names, s.nn_names if sample_nn else [], out, model, s.ode_base, s.nn_base, s.om, data)

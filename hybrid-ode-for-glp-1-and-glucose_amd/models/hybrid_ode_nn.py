@@ -1035,6 +1035,33 @@ class HybridODENN(nn.Module):
         return elbo, {"elbo": elbo, "kl": kl.to(self.device), "log_likelihood": log_lik.to(self.device)}
 
     # ------------------------------------------------------------------ loss
+    def data_nll(self, batch: Dict[str, torch.Tensor], observation=None, solver: str = "dopri5", rtol: float = 1e-6,
+                 atol: float = 1e-8, dtype=torch.float32) -> torch.Tensor:
+        """Negative log-likelihood of an INCOMPLETE batch under an inference.observation.ObservationModel (default: fixed
+        sigma = 1), up to the model's `log_norm()`: NaN observations, or those false in batch["observation_mask"], are missing;
+        per-state sigma (noise="fixed") or the noise integrated out (noise="marginal").  A fp64 scalar on the compute device,
+        differentiable through the adjoint: the solve is _SolveFn, the likelihood and its cotangent one launch of
+        hode_obs_nll_sets.  `dtype`: the precision of the solve (the module's parameters are cast to it)."""
+        from inference.observation import ObservationModel, _ObsNllFn
+        self._check_supported()
+        dev = _compute_device()
+        method = _SOLVERS.get(str(solver).lower())
+        if method is None:
+            raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+        om = ObservationModel() if observation is None else observation
+        x0, t, ins = self._prep_inputs(batch["initial_state"], batch["time_points"], batch.get("external_inputs"), dev)
+        if tuple(batch["observations"].shape) != (x0.shape[0], t.shape[-1], 6):
+            raise ValueError("observations must be [B, T, 6] on the grid of time_points")
+        om.prepare(batch["observations"], batch.get("observation_mask"), dev, dtype)
+        nn_flat, ode_vec = self._params_on(dev)
+        cast = lambda v: None if v is None else v.to(dtype).contiguous()          # noqa: E731
+        info, nl = {}, self.nn_residual
+        y = _SolveFn.apply(cast(x0), cast(nn_flat), cast(ode_vec), cast(t), cast(ins["meal"]), cast(ins["tVNS"]), cast(ins["GD"]),
+                           nl.hidden_dim, nl.hip_layers, method, float(rtol), float(atol), 1, info, self.tape_steps)
+        self.last_solve_info = info
+        self._warn_failures(info)
+        return _ObsNllFn.apply(y, om)
+
     def loss(self, batch: Dict[str, torch.Tensor], lambda1: float = 1.0, lambda2: float = 1.0,
              use_physics_loss: bool = True) -> torch.Tensor:
         """total = data + lambda1 * physics + lambda2 * reg  (hybrid_ode_nn.py:263-351).

@@ -348,6 +348,35 @@ int hode_mse_sets_f32(void *stream, int n_sets, int64_t len, const float *y, con
 int hode_mse_sets_f64(void *stream, int n_sets, int64_t len, const double *y, const double *obs, double scale,
                       double *loss_sum, double *gy);
 
+/* ---- Observation model (inference/observation.py): the negative log-likelihood of incomplete data with per-state noise, and
+ *      its cotangent, per parameter set.  y[n_sets][len] and obs[len] as for hode_mse_sets_*; len = n_traj * T * 6, element i
+ *      belongs to state i % 6.  Entry i is OBSERVED when obs[i] is finite and, with a mask (uint8[len], NULL = finiteness
+ *      only), mask[i] != 0; an unobserved entry may hold anything (NaN included): it adds exactly 0 to every sum and gets gy = 0.
+ *      With S_k = the sum of (y - obs)^2 over the observed entries of state k:
+ *        HODE_OBS_FIXED     nll = sum_k w[k] S_k / 2 (w[k] = 1 / sigma_k^2),            gy = w[k] (y - obs);
+ *        HODE_OBS_MARGINAL  sigma_k^2 ~ InvGamma(a[k], b[k]) integrated out, n[k] = the number of observed entries of state k
+ *                           in the WHOLE set: nll = sum_{n[k] > 0} (a[k] + n[k]/2) log(b[k] + S_k/2),
+ *                           gy = (a[k] + n[k]/2) / (b[k] + S_k/2) (y - obs); a state with n[k] = 0 adds 0 and gets gy = 0.
+ *      w, a, b, n: HOST double[6] (w: fixed mode, the other three NULL; a, b, n: marginal mode, w NULL).
+ *      sse: double[n_sets][6], the S_k, ACCUMULATED like loss_sum of hode_mse_sets; loss_sum: double[n_sets], nll ACCUMULATED
+ *      (may be NULL); gy[n_sets][len] (may be NULL).  A non-finite y at an observed entry makes sse and loss_sum non-finite.
+ *      flags: 0 = everything in one launch (sums added to sse, then nll and gy from the totals: zero sse before a whole set);
+ *      for a set cut into pieces, HODE_OBS_SUMS_ONLY adds the piece's sums to sse and touches nothing else, and
+ *      HODE_OBS_FROM_SSE takes sse as finished: nll (add it with ONE piece of the set, NULL for the others) and the piece's gy.
+ *      In fixed mode flags = 0 per piece is enough: its nll is that of the call's own sums.  One workgroup per set, sums reduced
+ *      in a fixed order: the same call gives the same bits, and 0 equals SUMS_ONLY then FROM_SSE bit for bit on a whole set.
+ *      Unaligned pointers and any len are fine. */
+#define HODE_OBS_FIXED 0
+#define HODE_OBS_MARGINAL 1
+#define HODE_OBS_SUMS_ONLY 1
+#define HODE_OBS_FROM_SSE 2
+int hode_obs_nll_sets_f32(void *stream, int n_sets, int64_t len, const float *y, const float *obs, const uint8_t *mask, int mode,
+                          int flags, const double *w, const double *a, const double *b, const double *n, double *sse,
+                          double *loss_sum, float *gy);
+int hode_obs_nll_sets_f64(void *stream, int n_sets, int64_t len, const double *y, const double *obs, const uint8_t *mask, int mode,
+                          int flags, const double *w, const double *a, const double *b, const double *n, double *sse,
+                          double *loss_sum, double *gy);
+
 /* ---- trajectory start: p = M^{1/2} xi (xi ~ N(0, 1), stream `iter`), ke0 = p^T minv p / 2, z0 = z, g0 = g, U0 = U,
  *      eps = exp(log_eps) * (1 + jitter * (2u - 1)) (u uniform, same stream), failed = 0. */
 int hode_hmc_refresh_f32(void *stream, int C, int D, int ld, uint64_t seed, uint32_t iter, double jitter, const float *minv,
