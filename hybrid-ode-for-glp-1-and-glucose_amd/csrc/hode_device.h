@@ -273,14 +273,9 @@ template <typename R> __device__ __forceinline__ int wcol(int r, int lane)
     else return r;
 }
 
-// Row stride of the LDS staging area used to permute a weight row into rotating-operand order.
-constexpr int kStageStride = kMaxH + 1;
-constexpr int kStageElems = (kMaxH / 2) * kStageStride;      // two passes of 32 lanes: 8.3 KB instead of 16.6 KB per wave
-
-// Load one parameter set into registers.  `stage` = wave-private LDS scratch of kStageElems reals (fp32 only;
-// may be nullptr for fp64): every lane reads its weight row with coalesced 16-byte loads, drops it into LDS
-// and reads it back in the lane-dependent rotated order -- no per-lane gather from global memory (which
-// cost 630 B/lane of scratch spills = 170 MB of extra HBM traffic per launch) and no long-lived temporaries.
+// Load one parameter set into registers: every lane gathers its weights straight from L2 in the lane-dependent rotated order (the
+// hidden layers below; a coalesced load + LDS permutation measured the same, profiles/r04_fwd_sizes_staged.log, and cost 8.3 KB of LDS
+// per wave).
 // Output layer in rotating order (fp32): lane (r, i) = lane 16 r + i keeps, for output o = i & 7,
 //     w5r[n] = Wout[o][16 r + ((i - n) & 15)]   n = 0..7        (zero for o >= 6)
 // so that sum_n row_ror:n(h) * w5r[n] -- 8 FMAs on the activation vector in its natural layout -- is one half of the lane's
@@ -327,7 +322,7 @@ __device__ __forceinline__ void mlp_load_edges(WT &W, const R *__restrict__ p, i
 }
 
 template <typename R, int NL>
-__device__ __forceinline__ void mlp_load(MlpRegs<R, NL> &W, const R *__restrict__ p, int H, int lane, R *stage)
+__device__ __forceinline__ void mlp_load(MlpRegs<R, NL> &W, const R *__restrict__ p, int H, int lane)
 {
     // branch-free: out-of-range lanes / columns read a clamped (valid) address and are zeroed
     const R live = (lane < H) ? R(1) : R(0);
@@ -345,7 +340,6 @@ __device__ __forceinline__ void mlp_load(MlpRegs<R, NL> &W, const R *__restrict_
             // row-block order (mlp_hidden_blk): lane (r, i) = lane 16 r + i keeps, for w = 0..3 and n = 0..15,
             //     weight (w, n) = W_l[16 w + i][16 r + ((i - n) & 15)]    -> half (w >> 1) of the pair wh[l][2 n + (w & 1)]
             // gathered straight from L2 (192 dword loads per lane and trajectory, ~0.5 % of a 241-point solve)
-            (void)stage;
             (void)row;
             const int i = lane & 15, r = lane >> 4;
 #pragma unroll
@@ -361,7 +355,6 @@ __device__ __forceinline__ void mlp_load(MlpRegs<R, NL> &W, const R *__restrict_
                 }
             }
         } else {
-            (void)stage;
             if (H == kMaxH) {
                 const double2 *r2 = reinterpret_cast<const double2 *>(row);
 #pragma unroll
@@ -891,8 +884,42 @@ __device__ __forceinline__ float out_rot(const float (&w)[8], float b5m, float h
 static __device__ unsigned long long g_ft[4096 * 8];
 static __device__ unsigned g_ft_n;
 #define HODE_FT(i, v) if (ft_on) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ft[i]), "+v"(v))
+// ... and the LIFETIME of every wave of a forward launch (tools/fwd_trace.py --lifetimes), one record of 8 words per workgroup:
+//   0 entry | 1 after the weight prologue | 2, 3, 4 grid index T/4, T/2, 3T/4 | 5 exit        (s_memtime, shader clock of the wave's XCC)
+//   6 HW_REG_HW_ID (wave slot, SIMD, CU, SH, SE) | HW_REG_XCC_ID << 32
+//   7 blockIdx.x | low word of s_memrealtime at exit << 32 (100 MHz, ONE counter for the chip: the XCCs' shader clocks are not aligned)
+// written by lane 0 with vector stores; launches of more than kWlWaves workgroups record the first kWlWaves
+constexpr int kWlWaves = 8192;
+static __device__ unsigned long long g_wl[kWlWaves * 8];
+__device__ __forceinline__ void wl_put(int i, unsigned long long v)
+{
+    if ((threadIdx.x & 63) == 0 && threadIdx.x < 64 && blockIdx.x < (unsigned)kWlWaves) g_wl[(size_t)blockIdx.x * 8 + i] = v;
+}
+__device__ __forceinline__ unsigned long long wl_clock()
+{
+    unsigned long long c;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(c));
+    return c;
+}
+__device__ __forceinline__ void wl_stamp(int i) { wl_put(i, wl_clock()); }
+__device__ __forceinline__ void wl_exit()
+{
+    unsigned hw, xcc;
+    unsigned long long rt;
+    wl_stamp(5);
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)\n\ts_memrealtime %2\n\ts_waitcnt lgkmcnt(0)"
+                 : "=s"(hw), "=s"(xcc), "=s"(rt));
+    wl_put(6, (unsigned long long)hw | ((unsigned long long)xcc << 32));
+    wl_put(7, (unsigned long long)blockIdx.x | (rt << 32));
+}
+#define HODE_WL(i) wl_stamp(i)
+#define HODE_WL_EXIT() wl_exit()
+#define HODE_WL_GRID(k, T) do { if ((k) == (T) / 4) wl_stamp(2); else if ((k) == (T) / 2) wl_stamp(3); else if ((k) == 3 * (T) / 4) wl_stamp(4); } while (0)
 #else
 #define HODE_FT(i, v)
+#define HODE_WL(i)
+#define HODE_WL_EXIT()
+#define HODE_WL_GRID(k, T)
 #endif
 template <typename R, int NL, bool KEEP, typename WT, typename ACTS = MlpActs<R, NL>>
 __device__ __forceinline__ R rhs_eval(const WT &W, const OdeP<R> &o, R t, R Y, R meal, R tvns,

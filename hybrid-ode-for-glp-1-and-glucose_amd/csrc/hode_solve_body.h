@@ -128,13 +128,46 @@ template <int J = 1> __device__ __forceinline__ float err_sum(const float (&K)[7
 }
 }  // namespace dp54c
 
+// Issue priority of a wave from the share of its work that is still ahead of it (PACE, the register kernels of hode_solve_fwd.hip: one
+// wave per workgroup, two waves per SIMD, no barrier between them).  The SIMD arbitrates vector issue between its two waves by priority
+// and then by AGE: with equal priorities the older wave runs nearly unimpeded, finishes first, and its partner ends the launch alone at
+// the lone-wave rate (63 % of the pair's throughput, profiles/r04_fwd_sizes.log).  Here the wave that is BEHIND outranks its partner, so
+// partners converge and end within the last level's share of a trajectory of each other; a wave of a second round that starts beside a
+// half-finished partner leads until it has caught up.  No communication: `left` and `total` are the wave's own grid intervals, all of
+// it scalar work (s_cmp / s_cbranch / s_setprio: no VGPR, no scratch).
+//   levels: left > total/2 -> 3, > total/8 -> 2, > total/32 -> 1, else 0 (geometric: the distance two partners can be apart halves
+//   with every level, and a wave crosses only three boundaries per trajectory).  Tried on the wave-lifetime log
+//   (tools/fwd_trace.py --lifetimes; DESIGN.md section 6.2 has the figures): linear quarters (3/4, 1/2, 1/4) and a two-level form
+//   (left > total/2 -> 1).
+__device__ __forceinline__ void pace_prio(int left, int total)
+{
+    left = __builtin_amdgcn_readfirstlane(left);
+    total = __builtin_amdgcn_readfirstlane(total);
+#if defined(HODE_FWD_PACE_LEVELS) && HODE_FWD_PACE_LEVELS == 4          // experiment builds (tools/build_variant.sh): linear quarters
+    if (4 * left > 3 * total) __builtin_amdgcn_s_setprio(3);
+    else if (2 * left > total) __builtin_amdgcn_s_setprio(2);
+    else if (4 * left > total) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+#elif defined(HODE_FWD_PACE_LEVELS) && HODE_FWD_PACE_LEVELS == 2        // two levels
+    if (2 * left > total) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+#else
+    if (2 * left > total) __builtin_amdgcn_s_setprio(3);
+    else if (8 * left > total) __builtin_amdgcn_s_setprio(2);
+    else if (32 * left > total) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+#endif
+}
+
 // rows  [8][64] tableau coefficient rows, cvec [8] tableau nodes (LDS, shared by the workgroup)
 // ybuf  [64 + 8] output staging of THIS wave (LDS)
 // rhs   the right-hand side functor of trajectory b's parameter set; o = its 17 mechanistic constants (Hill term)
-template <typename R, int METHOD, bool TAPE, bool GD, typename RHS>
+// PACE  set the wave's issue priority at the top of every grid interval (pace_prio): pace_after = the grid intervals of the trajectories
+//       this wave integrates AFTER this one (the MULTI loop), pace_total = those of all its trajectories; 0, 0 = this trajectory alone
+template <typename R, int METHOD, bool TAPE, bool GD, bool PACE = false, typename RHS>
 __device__ __forceinline__ void solve_one(const SolveArgs<R> &a, const int b, const RHS &rhs, const OdeP<R> &o,
                                           const R *__restrict__ rows, const R *__restrict__ cvec, R *__restrict__ ybuf,
-                                          const int lane)
+                                          const int lane, const int pace_after = 0, const int pace_total = 0)
 {
     const int c8 = lane & 7, grp = lane >> 3;
     const int T = a.T;
@@ -210,6 +243,8 @@ __device__ __forceinline__ void solve_one(const SolveArgs<R> &a, const int b, co
     grid_at(1, t1, m1, v1, d1);
     t2 = t1, m2 = m1, v2 = v1, d2 = d1;
     for (; k + 1 < T && st == HODE_ST_OK; ++k, t0 = t1, m0 = m1, v0 = v1, d0 = d1, t1 = t2, m1 = m2, v1 = v2, d1 = d2) {
+        if constexpr (PACE) pace_prio(pace_after + T - 1 - k, pace_total > 0 ? pace_total : T - 1);
+        HODE_WL_GRID(k, T);
         const R len = t1 - t0;
         if (!(len > R(0))) {                  // repeated grid time: copy the state
             grid_at(k + 2, t2, m2, v2, d2);

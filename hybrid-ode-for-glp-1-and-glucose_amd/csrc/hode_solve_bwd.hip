@@ -558,7 +558,7 @@ __global__ __launch_bounds__(256, 1) void rhs_bwd_kernel(const RhsArgs<R> a)
     const int lane = threadIdx.x & 63;
     const int wave = first_lane((int)(threadIdx.x >> 6));
     MlpRegs<R, NL> W;
-    mlp_load<R, NL>(W, a.nn_p, a.H, lane, wt + (size_t)wave * kStageElems);   // the image area doubles as staging
+    mlp_load<R, NL>(W, a.nn_p, a.H, lane);
     OdeP<R> o;
     ode_load(o, a.ode_p);
     __syncthreads();
@@ -646,7 +646,6 @@ template <typename R, int NL> static int launch_rhs_bwd_nl(hipStream_t s, const 
     if (blocks > 256) blocks = 256;
     if (blocks < 1) return HODE_OK;
     size_t lds = (size_t)(NL > 1 ? NL - 1 : 1) * kMaxH * kMaxH * sizeof(R);
-    if (lds < 4 * (size_t)kStageElems * sizeof(R)) lds = 4 * (size_t)kStageElems * sizeof(R);
     {
         const size_t red = ((size_t)(NL > 1 ? NL - 1 : 0) * kMaxH + EdgeSlots<NL>::count + 1) * kWave * sizeof(R);   // the workgroup reduction
         if (lds < red) lds = red;

@@ -13,13 +13,16 @@ namespace hode {
 // step, a dozen evaluations each) hand every wave `chunk` consecutive trajectories, so that the 54 KB of weights are gathered from L2
 // once per wave and not once per trajectory (half of such a launch's time).  A separate instantiation: the loop is kept out of the
 // kernels every other launch runs.
-template <typename R, int NL, int METHOD, int LB, bool TAPE, bool GD, bool MULTI>
+// PACE: every wave sets its issue priority from the share of its own work that is left (pace_prio, hode_solve_body.h), so that the two
+// waves of a SIMD reach the end of the launch together.  The product library always paces; the lab library and experiment builds can
+// switch it off for A/B runs (fwd_pace() below, -DHODE_FWD_NOPACE).
+template <typename R, int NL, int METHOD, int LB, bool TAPE, bool GD, bool MULTI, bool PACE>
 __global__ __launch_bounds__(64, LB) void solve_fwd_kernel(const SolveArgs<R> a, const int chunk)
 {
+    HODE_WL(0);
     __shared__ R rows[8 * kWave];             // tableau coefficient rows (hode_device.h)
     __shared__ R cvec[8];                     // tableau nodes c[s] as reals
     __shared__ R ybuf[kWave + 8];             // output staging: rows of 6 reals are gathered into 256-byte stores
-    __shared__ R wstage[(sizeof(R) == 4) ? kStageElems : 1];   // weight-row permutation scratch (prologue only)
     const int lane = threadIdx.x;
     const int b0 = MULTI ? blockIdx.x * chunk : blockIdx.x;                 // one wave == one trajectory (MULTI: one after the other)
     const int set = b0 / (a.B / a.n_sets);
@@ -27,23 +30,38 @@ __global__ __launch_bounds__(64, LB) void solve_fwd_kernel(const SolveArgs<R> a,
     tableau_rows_store<R>(rows, METHOD, lane, 64);
     if (lane < 8) cvec[lane] = (R)kTableau[METHOD].c[lane];
     MlpRegs<R, NL> W;
-    mlp_load<R, NL>(W, a.nn_p + (size_t)set * a.nn_stride, a.H, lane, wstage);
+    mlp_load<R, NL>(W, a.nn_p + (size_t)set * a.nn_stride, a.H, lane);
     OdeP<R> o;
     ode_load(o, a.ode_p + 17 * set);
     __syncthreads();
+    HODE_WL(1);
     const RhsRegs<R, NL, MlpRegs<R, NL>> rhs{W, o, lane};
     if constexpr (MULTI) {
         const int b1 = (b0 + chunk < a.B) ? b0 + chunk : a.B;
+        const int per = a.T - 1;              // grid intervals of one trajectory; the pace is taken over the whole chunk
 #pragma unroll 1
-        for (int b = b0; b < b1; ++b) solve_one<R, METHOD, TAPE, GD>(a, b, rhs, o, rows, cvec, ybuf, lane);
+        for (int b = b0; b < b1; ++b) solve_one<R, METHOD, TAPE, GD, PACE>(a, b, rhs, o, rows, cvec, ybuf, lane, (b1 - 1 - b) * per, (b1 - b0) * per);
     } else {
-        solve_one<R, METHOD, TAPE, GD>(a, b0, rhs, o, rows, cvec, ybuf, lane);
+        solve_one<R, METHOD, TAPE, GD, PACE>(a, b0, rhs, o, rows, cvec, ybuf, lane);
     }
+    HODE_WL_EXIT();
 }
 
-template <typename R, int NL, int METHOD, bool TAPE, bool GD>
+#ifdef HODE_LAB
+static bool fwd_pace();
+#endif
+
+template <typename R, int NL, int METHOD, bool TAPE, bool GD, bool PACE = true>
 static void launch_one(hipStream_t s, const SolveArgs<R> &a)
 {
+#if defined(HODE_LAB) || defined(HODE_FWD_NOPACE)
+    if constexpr (PACE) {
+#ifdef HODE_LAB
+        if (!fwd_pace())
+#endif
+            return launch_one<R, NL, METHOD, TAPE, GD, false>(s, a);
+    }
+#endif
     // waves per SIMD the register budget allows: 211 weight registers for 3 hidden matrices -> 2; fewer layers -> more
     constexpr int LB = (sizeof(R) == 4) ? (NL >= 3 ? 2 : (NL == 2 ? 3 : 4)) : 1;
     if constexpr (!TAPE && !GD && METHOD == HODE_METHOD_DP54 && sizeof(R) == 4) {
@@ -51,11 +69,21 @@ static void launch_one(hipStream_t s, const SolveArgs<R> &a)
         // (the benchmark batch as ONE round of 2 048 waves with two trajectories each was measured too: 3.10 against 3.01 ms)
         if (a.T <= 4 && a.n_sets == 1 && a.B > 8192) {
             const int chunk = (a.B + 8191) / 8192;
-            hipLaunchKernelGGL((solve_fwd_kernel<R, NL, METHOD, LB, TAPE, GD, true>), dim3((a.B + chunk - 1) / chunk), dim3(64), 0, s, a, chunk);
+            hipLaunchKernelGGL((solve_fwd_kernel<R, NL, METHOD, LB, TAPE, GD, true, PACE>), dim3((a.B + chunk - 1) / chunk), dim3(64), 0, s, a, chunk);
             return;
         }
+#ifdef HODE_FWD_ONE_ROUND
+        // experiment builds (-DHODE_FWD_ONE_ROUND=<longest chunk>): a batch of more than one round of the 2 048 wave slots as ONE round of
+        // waves with ceil(B / 2 048) trajectories each -- one weight prologue and one dispatch per slot
+        constexpr int kWaveSlots = 2048;      // 256 CUs x 4 SIMDs x 2 waves of this kernel
+        if (a.n_sets == 1 && a.B > kWaveSlots && (a.B + kWaveSlots - 1) / kWaveSlots <= HODE_FWD_ONE_ROUND) {
+            const int chunk = (a.B + kWaveSlots - 1) / kWaveSlots;
+            hipLaunchKernelGGL((solve_fwd_kernel<R, NL, METHOD, LB, TAPE, GD, true, PACE>), dim3((a.B + chunk - 1) / chunk), dim3(64), 0, s, a, chunk);
+            return;
+        }
+#endif
     }
-    hipLaunchKernelGGL((solve_fwd_kernel<R, NL, METHOD, LB, TAPE, GD, false>), dim3(a.B), dim3(64), 0, s, a, 1);
+    hipLaunchKernelGGL((solve_fwd_kernel<R, NL, METHOD, LB, TAPE, GD, false, PACE>), dim3(a.B), dim3(64), 0, s, a, 1);
 }
 
 template <typename R, int NL>
@@ -83,6 +111,15 @@ static char fwd_mode()
         const char *e = getenv("HODE_FWD");
         if (e == nullptr) return '\0';
         return (e[0] == 'r' && e[1] == 'o') ? 'R' : e[0];
+    }();
+    return v;
+}
+// HODE_FWD_PACE=off: the register kernels without the priority pacing (A/B timings; tests/test_fwd_pacing_gpu.py compares the bits)
+static bool fwd_pace()
+{
+    static const bool v = [] {
+        const char *e = getenv("HODE_FWD_PACE");
+        return !(e != nullptr && (e[0] == '0' || (e[0] == 'o' && e[1] == 'f')));
     }();
     return v;
 }
@@ -117,5 +154,12 @@ extern "C" int hode_lab_fwd_trace(unsigned long long *dst, int n_words, unsigned
 {
     if (hipMemcpyFromSymbol(count, HIP_SYMBOL(hode::g_ft_n), sizeof(unsigned)) != hipSuccess) return -1;
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(hode::g_ft), sizeof(unsigned long long) * (size_t)n_words) == hipSuccess ? 0 : -1;
+}
+// the wave-lifetime records of the last forward launch: n_waves <= kWlWaves records of 8 words (hode_device.h, g_wl)
+extern "C" int hode_lab_fwd_lifetimes(unsigned long long *dst, int n_waves)
+{
+    if (n_waves < 0 || n_waves > hode::kWlWaves) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(hode::g_wl), sizeof(unsigned long long) * 8 * (size_t)n_waves) == hipSuccess ? 0 : -1;
 }
 #endif

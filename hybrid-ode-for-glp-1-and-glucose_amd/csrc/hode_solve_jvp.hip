@@ -119,7 +119,7 @@ __global__ __launch_bounds__(64 * kJvpWaves, 1) void solve_jvp_kernel(const JvpA
     const int rowb = (method == HODE_METHOD_DP54) ? 6 : 7;   // solution weights: DP5(4) row 6 (FSAL row), RK4 row 7
 
     MlpRegs<R, NL> W;
-    mlp_load<R, NL>(W, a.nn_p + (size_t)set * a.P, a.H, lane, nullptr);
+    mlp_load<R, NL>(W, a.nn_p + (size_t)set * a.P, a.H, lane);
     OdeP<R> o;
     ode_load(o, a.ode_p + 17 * set);
 

@@ -33,7 +33,7 @@ F = {
     "TAPE_MS": f"{tape['kernel_ms']:.2f}", "ADJ_MS": f"{adj['kernel_ms']:.2f}", "ADJ_FRAC": f"{adj['frac']:.3f}", "TAPE_FRAC": f"{tape['frac']:.3f}",
     "TRAIN_MS": f"{tr['ms_per_step']:.2f}", "TRAIN_TPS": f"{tr['value'] / 1e3:.0f}",
     "TAPE_GB": "n/a" if tape["traffic"] is None else f"{tape['traffic'] / 1e9:.2f}", "ADJ_GB": "n/a" if adj["traffic"] is None else f"{adj['traffic'] / 1e9:.2f}",
-    "K_FWD": f"{k('solve_fwd_kernel<float, 4, 0, 2, false, false>'):.3f}", "K_TAPE": f"{k('solve_fwd_kernel<float, 4, 0, 2, true, false>'):.3f}",
+    "K_FWD": f"{k('solve_fwd_kernel<float, 4, 0, 2, false, false,'):.3f}", "K_TAPE": f"{k('solve_fwd_kernel<float, 4, 0, 2, true, false,'):.3f}",
     "K_ADJ": f"{k('solve_bwd_ws_kernel<4, 2'):.3f}",
     "CLSF": f"{d['class_path']['forward']['ms_events']:.2f}", "CLS32": f"{cls[(32, 61)]['ms_wall']:.2f}", "CLS4096": f"{cls[(4096, 241)]['ms_wall']:.1f}",
     "SOBOL_MS": f"{1e3 * d['sobol']['seconds_with_outputs']:.1f}", "SOBOL_TPS": f"{d['sobol']['value'] / 1e6:.1f}",
