@@ -160,26 +160,21 @@ class _PatientSolver:
     network copy per patient, as HMC runs its chains)."""
 
     def __init__(self, model, batch, names, dtype, solver, rtol, atol, max_steps):
-        from models.hybrid_ode_nn import STATE_NAMES, _SOLVERS, _compute_device, _small_tape_steps, _tape_steps
+        from models.hybrid_ode_nn import STATE_NAMES, _compute_device, _device_batch, _method, _taped_steps
         from models.ode_core import ODE_PARAM_NAMES
         model._check_supported()
         self.dev = dev = _compute_device()
         self.dt = dtype
-        x0, t, ins = model._prep_inputs(batch["initial_state"], batch["time_points"], batch.get("external_inputs"), dev)
-        cast = lambda v: None if v is None else v.to(dtype).contiguous()                            # noqa: E731
-        self.x0, self.t = cast(x0), cast(t)
-        self.meal, self.tvns, self.gd = cast(ins["meal"]), cast(ins["tVNS"]), cast(ins["GD"])
+        self.x0, self.t, self.meal, self.tvns, self.gd = _device_batch(model, batch, dev, dtype)
         self.B, self.T = self.x0.shape[0], self.t.shape[-1]
         nl = model.nn_residual
         self.H, self.L = nl.hidden_dim, nl.hip_layers
-        self.method = _SOLVERS.get(str(solver).lower())
-        if self.method is None:
-            raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+        self.method = _method(solver)
         self.rtol, self.atol = float(rtol), float(atol)
         with torch.no_grad():
             nn_flat, ode_vec = model._params_on(dev)
-        self.nn = cast(nn_flat.detach()).repeat(self.B).contiguous()
-        self.ode_base = cast(ode_vec.detach())
+        self.nn = nn_flat.detach().to(dtype).repeat(self.B).contiguous()
+        self.ode_base = ode_vec.detach().to(dtype).contiguous()
         self.cols = []                        # ("ode", index) / ("x0", index) per fit coordinate
         for n in names:
             if n.startswith("x0:"):
@@ -197,9 +192,8 @@ class _PatientSolver:
             (self.v_ode if kind == "ode" else self.v_x0)[:, k, j] = 1.0
         self.has_ode = any(c[0] == "ode" for c in self.cols)
         self.has_x0 = any(c[0] == "x0" for c in self.cols)
-        self.max_steps = int(max_steps) if max_steps is not None else (
-            _small_tape_steps(self.B, self.T, self.method, self.x0.element_size(), self.L, self.H, model.tape_steps)
-            or _tape_steps(self.T, self.method, model.tape_steps))
+        self.max_steps = int(max_steps) if max_steps is not None else _taped_steps(
+            self.B, self.T, self.method, self.x0.element_size(), self.L, self.H, model.tape_steps)
         self.tape = None
 
     def theta0(self):

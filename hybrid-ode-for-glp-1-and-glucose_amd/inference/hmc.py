@@ -13,6 +13,7 @@ cotangent come from hode_mse_sets, and everything else a step does to the chains
 test, dual averaging, draws, the mass matrix) is a HIP kernel of csrc/hode_hmc.hip.  Step sizes are per chain (dual
 averaging, Stan's constants), the diagonal mass matrix is pooled across chains over Stan's doubling warm-up windows."""
 import math
+from functools import partial
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -57,7 +58,7 @@ class _Sampler:
     def __init__(self, model, data, n_chains, noise_sigma=1.0, ode_priors=None, sample_nn=True, seed=0, solver="dopri5",
                  rtol=1e-6, atol=1e-8, dtype=torch.float32, jitter=0.1, noise="fixed", noise_prior=None):
         from inference.observation import ObservationModel
-        from models.hybrid_ode_nn import _SOLVERS, _compute_device
+        from models.hybrid_ode_nn import _compute_device, _device_batch, _method
         from models.ode_core import ODE_PARAM_NAMES
         self.om = ObservationModel(noise_sigma, noise, noise_prior)          # validates before any device is needed
         model._check_supported()
@@ -66,9 +67,7 @@ class _Sampler:
         nl = model.nn_residual
         self.H, self.L = nl.hidden_dim, nl.hip_layers
         self.P = hode.n_params(self.H, self.L)
-        self.method = _SOLVERS.get(str(solver).lower())
-        if self.method is None:
-            raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+        self.method = _method(solver)
         self.rtol, self.atol, self.seed, self.jitter = float(rtol), float(atol), int(seed) & (2 ** 64 - 1), float(jitter)
         priors = dict(REFERENCE_PRIORS if ode_priors is None else ode_priors)
         for k in priors:
@@ -109,12 +108,9 @@ class _Sampler:
         self.lik_scale = 0.5 / float(self.om.sigma[0]) ** 2
         self.loss_sum = torch.zeros(C, **f64)
         self.obs_kernel = False
-        self.has_data = data is not None
+        self.data, self.has_data = data, data is not None
         if self.has_data:
-            x0, t, ins = model._prep_inputs(data["initial_state"], data["time_points"], data.get("external_inputs"), dev)
-            cast = lambda v: None if v is None else v.to(dtype).contiguous()              # noqa: E731
-            self.x0, self.t = cast(x0), cast(t)
-            self.meal, self.tvns, self.gd = cast(ins["meal"]), cast(ins["tVNS"]), cast(ins["GD"])
+            self.x0, self.t, self.meal, self.tvns, self.gd = _device_batch(model, data, dev, dtype)
             self.N, self.T = self.x0.shape[0], self.t.shape[-1]
             if tuple(data["observations"].shape) != (self.N, self.T, 6):
                 raise ValueError("observations must be [B, T, 6] on the grid of time_points")
@@ -127,67 +123,47 @@ class _Sampler:
                 self.lik_scale = 1.0
                 self.sse = torch.zeros(C, 6, **f64)
             self.status = torch.zeros(C, self.N, dtype=torch.int32, device=dev)
+            self.solve_args = (self.x0, self.t, self.meal, self.tvns, self.gd, self.ode_p, self.nn_p, self.H, self.L, self.method,
+                               self.rtol, self.atol)          # what _run_sets takes: the batch and the chains' parameter buffers
         self.gnn = self.gode = None
 
     # ------------------------------------------------------------------ the pieces of an iteration
     def evaluate(self, n_sets=None):
         """Likelihood sum of squares, its gradient and the solve statuses at the parameters in nn_p / ode_p: of all chains, or
         of the first n_sets parameter sets (the NUTS driver's compacted active chains); forward with tape -> hode_mse_sets (or
-        hode_obs_nll_sets: the negative log-likelihood of the observation model) -> adjoint, cut into tape-budget pieces the way
-        _gauss_lik_core cuts them."""
+        hode_obs_nll_sets: the negative log-likelihood of the observation model) -> adjoint, piece by piece under the tape
+        budget (models.hybrid_ode_nn._run_sets; this class supplies the cotangent of a piece)."""
         if not self.has_data:
             return
-        from models.hybrid_ode_nn import _pieces, _small_tape_steps, _solve_taped, _tape_budget, _tape_steps
-        C, N, T, P = self.C if n_sets is None else int(n_sets), self.N, self.T, self.P
-        elem = self.x0.element_size()
-        ts = self.model.tape_steps
-        steps = _small_tape_steps(C * N, T, self.method, elem, self.L, self.H, ts) or _tape_steps(T, self.method, ts)
-        per_traj = hode.capi.tape_nbytes(1, steps, elem, self.L, self.H)
-        cap = max(1, _tape_budget(self.dev, C * N * per_traj) // per_traj)
-        pieces = _pieces(C, N, cap)
-        one = len(pieces) == 1
+        import models.hybrid_ode_nn as HN
+        C, N = self.C if n_sets is None else int(n_sets), self.N
+        plan = HN._plan_sets(self.dev, C, N, self.T, self.method, self.x0.element_size(), self.L, self.H, self.model.tape_steps)
+        lo, hi = plan[1][0][2:]
         self.loss_sum.zero_()
-        want_nn, want_ode = self.sample_nn, self.n_ode > 0
-        if not one:
-            self.gnn = torch.zeros(C * P, dtype=self.dt, device=self.dev) if want_nn else None
-            self.gode = torch.zeros(C * 17, dtype=self.dt, device=self.dev) if want_ode else None
-            if self.status.shape[0] < C:                # a smaller one-piece evaluation left a view of its own statuses
-                self.status = torch.zeros(self.C, N, dtype=torch.int32, device=self.dev)
-        flags = 0
+        stat = []
+        cotangent = partial(self._mse_piece, stat)
         if self.obs_kernel:
             self.sse.zero_()
-            if self.om.marginal and pieces[0][3] - pieces[0][2] < N:
+            flags = 0
+            if self.om.marginal and hi - lo < N:
                 # a set cut into pieces: its cotangent needs the sums of the WHOLE set, so the pieces run once without a tape first
+                HN._run_sets(plan, partial(self._obs_piece, [], hode.capi.OBS_SUMS_ONLY), (False, False, False), *self.solve_args)
                 flags = hode.capi.OBS_FROM_SSE
-                for s0, s1, lo, hi in pieces:
-                    cut = lambda v: None if v is None else v[lo:hi]              # noqa: E731
-                    y = hode.solve_fwd(self.x0[lo:hi], self.t if self.t.dim() == 1 else self.t[lo:hi], cut(self.meal), cut(self.tvns),
-                                       cut(self.gd), self.ode_p[17 * s0:17 * s1], self.nn_p[P * s0:P * s1], self.H, self.L,
-                                       method=self.method, rtol=self.rtol, atol=self.atol, n_sets=1).y
-                    self.om.nll_sets(y.view(1, -1), None, self.sse[s0:s1], lo, hi, hode.capi.OBS_SUMS_ONLY)
-        tape = None
-        for s0, s1, lo, hi in pieces:
-            m = s1 - s0
-            rep = lambda v: None if v is None else (v[lo:hi].repeat(m, *([1] * (v.dim() - 1))) if m > 1 else v[lo:hi])  # noqa: E731
-            sol = _solve_taped(rep(self.x0), self.t if self.t.dim() == 1 else rep(self.t), rep(self.meal), rep(self.tvns), rep(self.gd),
-                               self.ode_p[17 * s0:17 * s1], self.nn_p[P * s0:P * s1], self.H, self.L, self.method, self.rtol,
-                               self.atol, m, steps, tape=tape)
-            tape = sol.tape
-            if self.obs_kernel:
-                ls = self.loss_sum[s0:s1] if flags == 0 or lo == 0 else None           # the finished sums' nll: once per set
-                gy = self.om.nll_sets(sol.y.view(m, -1), ls, self.sse[s0:s1], lo, hi, flags)
-            else:
-                gy = hode.capi.mse_sets(sol.y.view(m, -1), self.obs[lo:hi], self.lik_scale, self.loss_sum[s0:s1])
-            _, gn, go = sol.backward(gy.view_as(sol.y), want_gnn=want_nn, want_gode=want_ode)
-            if one:
-                self.gnn, self.gode = gn, go
-                self.status = sol.status.view(C, N)
-            else:
-                if gn is not None:
-                    self.gnn[P * s0:P * s1] += gn
-                if go is not None:
-                    self.gode[17 * s0:17 * s1] += go
-                self.status[s0:s1, lo:hi] = sol.status.view(m, hi - lo)
+            cotangent = partial(self._obs_piece, stat, flags)
+        _, self.gnn, self.gode = HN._run_sets(plan, cotangent, (False, self.sample_nn, self.n_ode > 0), *self.solve_args)
+        self.status = (stat[0] if len(stat) == 1 else torch.cat(stat)).view(C, N)
+
+    def _mse_piece(self, stat, sol, s0, s1, lo, hi):
+        stat.append(sol.status)
+        return hode.capi.mse_sets(sol.y.view(s1 - s0, -1), self.obs[lo:hi], self.lik_scale, self.loss_sum[s0:s1]).view_as(sol.y)
+
+    def _obs_piece(self, stat, flags, sol, s0, s1, lo, hi):
+        """The observation kernel on a piece.  OBS_SUMS_ONLY: the forward-only pass over slices of a set; OBS_FROM_SSE: their
+        cotangents from the finished sums, whose nll is taken once per set."""
+        stat.append(sol.status)
+        ls = None if flags == hode.capi.OBS_SUMS_ONLY or (flags and lo) else self.loss_sum[s0:s1]
+        gy = self.om.nll_sets(sol.y.view(s1 - s0, -1), ls, self.sse[s0:s1], lo, hi, flags)
+        return None if gy is None else gy.view_as(sol.y)
 
     def leapfrog(self, flags, kick=0.0):
         d = self.has_data
@@ -433,15 +409,33 @@ def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1
     mechanistic constants (default: the reference's seven); sample_nn: sample every MLP weight (prior N(0, 1)).  `device` is
     accepted for run_nuts compatibility: the work runs on the HIP device.  `progress(it, stats)`, if given, is called once per
     iteration (one host synchronisation)."""
-    if num_samples < 1 or num_warmup < 0 or n_chains < 1 or n_leapfrog < 1 or thin < 1:
-        raise ValueError("num_samples, n_chains, n_leapfrog, thin must be >= 1 and num_warmup >= 0")
+    def transition(s, it, warm, draws, stats, n_slots, slot):
+        s.refresh(it)
+        s.trajectory(n_leapfrog)
+        s.accept(hode.capi.HMC_ADAPT if warm else hode.capi.HMC_SAMPLE, it, target_accept, draws, stats, n_slots, slot)
+    return _run_schedule(lambda: _Sampler(model, data, n_chains, noise_sigma, ode_priors, sample_nn, seed, solver, rtol, atol, dtype,
+                                          jitter, noise, noise_prior),
+                         transition, n_stats=4, num_samples=num_samples, num_warmup=num_warmup, thin=thin, target_accept=target_accept,
+                         progress=progress, counts_ok=min(num_samples, n_chains, n_leapfrog, thin) >= 1,
+                         counts_message="num_samples, n_chains, n_leapfrog, thin must be >= 1 and num_warmup >= 0")
+
+
+def _run_schedule(make_sampler, transition, *, n_stats, num_samples, num_warmup, thin, target_accept, progress, counts_ok, counts_message,
+                  extra_stats=None, extra_progress=None):
+    """What run_hmc and run_nuts share: the argument checks (`counts_ok`: the sampler's counts are all >= 1, else ValueError
+    `counts_message`), the sampler of `make_sampler()`, Stan's warm-up schedule and the sampling iterations around
+    `transition(s, it, warm, draws, stats, n_slots, slot)` -- one iteration of all chains that adapts (warm) or records into
+    slot `slot` of draws / stats [C, n_slots, n_stats] (-1: not kept) -- and the result.  `extra_stats(stats array) -> dict`
+    names the sampler's own stat columns, `extra_progress(s) -> dict` adds its entries to what `progress` is told."""
+    if not counts_ok or num_warmup < 0:
+        raise ValueError(counts_message)
     if not 0.0 < target_accept < 1.0:
         raise ValueError("target_accept must lie in (0, 1)")
-    s = _Sampler(model, data, n_chains, noise_sigma, ode_priors, sample_nn, seed, solver, rtol, atol, dtype, jitter, noise, noise_prior)
+    s = make_sampler()
     C, D = s.C, s.D
     n_slots = (num_samples + thin - 1) // thin
-    draws = torch.empty(C, n_slots, D, dtype=dtype, device=s.dev)
-    stats = torch.empty(C, n_slots, 4, dtype=torch.float64, device=s.dev)
+    draws = torch.empty(C, n_slots, D, dtype=s.dt, device=s.dev)
+    stats = torch.empty(C, n_slots, n_stats, dtype=torch.float64, device=s.dev)
     cap = hode.capi
     s.initial_jitter()
     s.gradient()
@@ -454,9 +448,7 @@ def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1
         slot = -1
         if not warm and (it - num_warmup) % thin == 0:
             slot = (it - num_warmup) // thin
-        s.refresh(it)
-        s.trajectory(n_leapfrog)
-        s.accept(cap.HMC_ADAPT if warm else cap.HMC_SAMPLE, it, target_accept, draws, stats, n_slots, slot)
+        transition(s, it, warm, draws, stats, n_slots, slot)
         if warm and any(a <= it < b for a, b in wins):
             s.welford(cap.HMC_WELFORD_ACCUM)
         if warm and (it + 1) in ends:
@@ -466,8 +458,10 @@ def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1
         if warm and it + 1 == num_warmup:
             s.accept(cap.HMC_DA_FINISH, it)
         if progress is not None:
-            progress(it, {"step_size": s.log_eps.exp().mean().item()})
-    st = {"accept_prob": stats[..., 0].cpu().numpy(), "log_posterior": stats[..., 1].cpu().numpy(),
-          "divergent": stats[..., 2].cpu().numpy() > 0, "failed_solve": stats[..., 3].cpu().numpy() > 0,
-          "step_size": s.log_eps.exp().cpu().numpy(), "inv_mass": s.minv[:D].double().cpu().numpy()}
-    return HMCResult(draws, s.ode_names, s.nn_names if sample_nn else [], st, model, s.ode_base, s.nn_base, s.om, data)
+            progress(it, {"step_size": s.log_eps.exp().mean().item(), **(extra_progress(s) if extra_progress else {})})
+    st = stats.cpu().numpy()
+    out = {"accept_prob": st[..., 0], "log_posterior": st[..., 1], "divergent": st[..., 2] > 0, "failed_solve": st[..., 3] > 0}
+    out.update(extra_stats(st) if extra_stats else {})
+    out.update(step_size=s.log_eps.exp().cpu().numpy(), inv_mass=s.minv[:D].double().cpu().numpy())
+    return HMCResult(draws, s.ode_names, s.nn_names if s.sample_nn else [], out, s.model, s.ode_base, s.nn_base, s.om,
+                     s.data)

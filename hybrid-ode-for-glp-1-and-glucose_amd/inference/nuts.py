@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 import hode
-from inference.hmc import HMCResult, _Sampler, _windows
+from inference.hmc import HMCResult, _Sampler, _run_schedule
 
 __all__ = ["run_nuts"]
 
@@ -80,45 +80,19 @@ def run_nuts(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 
 
     The result's stats add tree_depth and n_leapfrog [chains, draws] (int) to run_hmc's, accept_prob is the tree's accept
     statistic, and trajectories_solved [iterations] counts the solves of every sampling and warm-up iteration."""
-    if num_samples < 1 or num_warmup < 0 or n_chains < 1 or thin < 1:
-        raise ValueError("num_samples, n_chains, thin must be >= 1 and num_warmup >= 0")
-    if not 0.0 < target_accept < 1.0:
-        raise ValueError("target_accept must lie in (0, 1)")
-    s = _NutsSampler(model, data, n_chains, max_tree_depth, noise_sigma=noise_sigma, ode_priors=ode_priors, sample_nn=sample_nn,
-                     seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter, noise=noise, noise_prior=noise_prior)
-    C, D = s.C, s.D
-    n_slots = (num_samples + thin - 1) // thin
-    draws = torch.empty(C, n_slots, D, dtype=dtype, device=s.dev)
-    stats = torch.empty(C, n_slots, 6, dtype=torch.float64, device=s.dev)
-    cap = hode.capi
-    s.initial_jitter()
-    s.gradient()
-    window = 0
-    s.find_step_size(window)
-    init, wins = _windows(num_warmup)
-    ends = {b: a for a, b in wins}
     solved = []
-    for it in range(num_warmup + num_samples):
-        warm = it < num_warmup
-        slot = -1
-        if not warm and (it - num_warmup) % thin == 0:
-            slot = (it - num_warmup) // thin
+
+    def transition(s, it, warm, draws, stats, n_slots, slot):
         s.transition(it)
         s.finish(warm, target_accept, draws, stats, n_slots, slot)
         solved.append(s.solved)
-        if warm and any(a <= it < b for a, b in wins):
-            s.welford(cap.HMC_WELFORD_ACCUM)
-        if warm and (it + 1) in ends:
-            s.welford(cap.HMC_WELFORD_FINISH)          # new M^-1, then a new step size and a fresh dual averaging
-            window += 1
-            s.find_step_size(window)
-        if warm and it + 1 == num_warmup:
-            s.accept(cap.HMC_DA_FINISH, it)
-        if progress is not None:
-            progress(it, {"step_size": s.log_eps.exp().mean().item(), "leaf_steps": s.leaf_steps})
-    st = stats.cpu().numpy()
-    out = {"accept_prob": st[..., 0], "log_posterior": st[..., 1], "divergent": st[..., 2] > 0, "failed_solve": st[..., 3] > 0,
-           "tree_depth": st[..., 4].astype(np.int64), "n_leapfrog": st[..., 5].astype(np.int64),
-           "step_size": s.log_eps.exp().cpu().numpy(), "inv_mass": s.minv[:D].double().cpu().numpy(),
-           "trajectories_solved": np.asarray(solved, dtype=np.int64)}
-    return HMCResult(draws, s.ode_names, s.nn_names if sample_nn else [], out, model, s.ode_base, s.nn_base, s.om, data)
+    res = _run_schedule(lambda: _NutsSampler(model, data, n_chains, max_tree_depth, noise_sigma=noise_sigma, ode_priors=ode_priors,
+                                             sample_nn=sample_nn, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype,
+                                             jitter=jitter, noise=noise, noise_prior=noise_prior),
+                        transition, n_stats=6, num_samples=num_samples, num_warmup=num_warmup, thin=thin, target_accept=target_accept,
+                        progress=progress, counts_ok=min(num_samples, n_chains, thin) >= 1,
+                        counts_message="num_samples, n_chains, thin must be >= 1 and num_warmup >= 0",
+                        extra_stats=lambda st: {"tree_depth": st[..., 4].astype(np.int64), "n_leapfrog": st[..., 5].astype(np.int64)},
+                        extra_progress=lambda s: {"leaf_steps": s.leaf_steps})
+    res.stats["trajectories_solved"] = np.asarray(solved, dtype=np.int64)
+    return res

@@ -40,6 +40,14 @@ _SOLVERS = {"dopri5": hode.METHOD_DP54, "rk45": hode.METHOD_DP54, "dop853": hode
             "radau": hode.METHOD_DP54, "bdf": hode.METHOD_DP54, "rk4": hode.METHOD_RK4}
 
 
+def _method(solver):
+    """The kernels' method code of a reference solver name."""
+    method = _SOLVERS.get(str(solver).lower())
+    if method is None:
+        raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+    return method
+
+
 def _compute_device() -> torch.device:
     if not torch.cuda.is_available():
         raise hode.HodeError("HybridODENN needs a HIP device: the solve/adjoint path has no CPU fallback")
@@ -131,6 +139,18 @@ def _small_tape_steps(n_traj, T, method, elem, L, H, override):
     return big if n_traj * hode.capi.tape_nbytes(1, big, elem, L, H) <= SMALL_TAPE_BYTES else None
 
 
+def _taped_steps(n_traj, T, method, elem, L, H, override):
+    """Accepted-step budget of a taped solve of `n_traj` trajectories: the no-grad budget while that tape is small."""
+    return _small_tape_steps(n_traj, T, method, elem, L, H, override) or _tape_steps(T, method, override)
+
+
+def _tape_cap(dev, steps, elem, L, H, n_traj=0):
+    """How many trajectories' tapes of `steps` steps fit the tape budget (at least one).  `n_traj`: how many the caller
+    has, which lets _tape_budget answer from its cache; 0 asks the allocator what fits NOW."""
+    per_traj = hode.capi.tape_nbytes(1, steps, elem, L, H)
+    return max(1, _tape_budget(dev, n_traj * per_traj) // per_traj)
+
+
 class _FlatNN(torch.autograd.Function):
     """The flat parameter vector the kernels take, WITHOUT the torch.cat of ten tensors per step: the ten parameters are views
     of one buffer (HybridODENN._nn_flat_store), forward hands that buffer out, backward cuts the gradient into ten views."""
@@ -219,11 +239,16 @@ class _Taped:
         for k, v in (gi or {}).items():
             if v is not None:
                 gin[k][idx] = v
-        if gn is not None:
-            P = gn.numel()
-            gnn[P * set_id:P * (set_id + 1)] += gn
-        if go is not None:
-            gode[17 * set_id:17 * (set_id + 1)] += go
+        _add_sets(gnn, gode, set_id, set_id + 1, gn, go)
+
+
+def _add_sets(gnn, gode, s0, s1, gn, go):
+    """Add the parameter gradients of the sets s0..s1-1 (either may be None) into the per-set buffers."""
+    if gn is not None:
+        P = gn.numel() // (s1 - s0)
+        gnn[P * s0:P * s1] += gn
+    if go is not None:
+        gode[17 * s0:17 * s1] += go
 
 
 def _solve_taped(x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol, n_sets, steps, tape=None):
@@ -273,10 +298,9 @@ class _SolveFn(torch.autograd.Function):
         # (x0, MLP, ODE constants) or the inputs meal / tVNS / GD (positions 4..6)
         need_tape = any(ctx.needs_input_grad[:3]) or any(ctx.needs_input_grad[4:7])
         B, T = x0.shape[0], t.shape[-1]
-        steps = (_small_tape_steps(B, T, method, x0.element_size(), L, H, tape_steps) if need_tape else None) or _tape_steps(T, method, tape_steps)
-        per_traj = hode.capi.tape_nbytes(1, steps, x0.element_size(), L, H)
-        budget = _tape_budget(x0.device, B * per_traj) if need_tape else 0
-        ctx.chunked = need_tape and B * per_traj > budget
+        steps = _taped_steps(B, T, method, x0.element_size(), L, H, tape_steps) if need_tape else None
+        need = B * hode.capi.tape_nbytes(1, steps, x0.element_size(), L, H) if need_tape else 0
+        ctx.chunked = need_tape and need > _tape_budget(x0.device, need)
         ctx.sol = None
         if need_tape and not ctx.chunked:
             sol = ctx.sol = _solve_taped(x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol, n_sets, steps)
@@ -289,8 +313,7 @@ class _SolveFn(torch.autograd.Function):
             sol = hode.solve_fwd(x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method=method, rtol=rtol, atol=atol,
                                  n_sets=n_sets)
         if ctx.chunked:
-            ctx.args = (x0, nn_flat, ode_vec, t, meal, tvns, gd, H, L, method, rtol, atol, n_sets, steps,
-                        per_traj)
+            ctx.args = (x0, nn_flat, ode_vec, t, meal, tvns, gd, H, L, method, rtol, atol, n_sets, steps)
         info["status"], info["nsteps"], info["nfev"] = sol.status, sol.nsteps, sol.nfev
         return sol.y
 
@@ -304,9 +327,9 @@ class _SolveFn(torch.autograd.Function):
             ctx.sol = None
             gin = r[3] if want_in else {}
             return (r[0] if need[0] else None, r[1], r[2], None) + tuple(gin.get(k) for k in hode.capi.INPUT_KEYS) + (None,) * 8
-        x0, nn_flat, ode_vec, t, meal, tvns, gd, H, L, method, rtol, atol, n_sets, steps, per_traj = ctx.args
+        x0, nn_flat, ode_vec, t, meal, tvns, gd, H, L, method, rtol, atol, n_sets, steps = ctx.args
         ctx.args = None
-        cap = max(1, _tape_budget(x0.device) // per_traj)      # what fits NOW (other tapes may have been freed or made)
+        cap = _tape_cap(x0.device, steps, x0.element_size(), L, H)      # what fits NOW (other tapes may have been freed or made)
         gy = gy.contiguous()
         B, P = x0.shape[0], nn_flat.numel() // n_sets
         G = B // n_sets                                   # trajectories per parameter set (contiguous groups)
@@ -328,10 +351,7 @@ class _SolveFn(torch.autograd.Function):
             gx0[lo:hi] = g0
             for k in want_in:
                 gin[k][lo:hi] = r[3][k]
-            if gn is not None:
-                gnn[P * s0:P * s1] += gn
-            if go is not None:
-                gode[17 * s0:17 * s1] += go
+            _add_sets(gnn, gode, s0, s1, gn, go)
         return (gx0 if need[0] else None, gnn, gode, None) + tuple(gin[k] for k in hode.capi.INPUT_KEYS) + (None,) * 8
 
 
@@ -361,63 +381,83 @@ def _pieces(n_sets, G, cap):
     return [(s, s + 1, a, min(a + cap, G)) for s in range(n_sets) for a in range(0, G, cap)]
 
 
+def _plan_sets(dev, n_sets, G, T, method, elem, L, H, tape_steps=None, grads=True):
+    """(accepted-step budget of the taped solves, pieces of _pieces) for n_sets parameter sets x G shared patients on a grid of
+    T points under the tape budget.  Without gradients nothing is taped: one piece."""
+    if not grads:
+        return _tape_steps(T, method, tape_steps), _pieces(n_sets, G, n_sets * G)
+    steps = _taped_steps(n_sets * G, T, method, elem, L, H, tape_steps)
+    return steps, _pieces(n_sets, G, _tape_cap(dev, steps, elem, L, H, n_sets * G))
+
+
+def _rep(v, lo, hi, m):
+    """Rows lo:hi of a tensor shared by the parameter sets (or None), once for each of the m sets of a piece."""
+    if v is None:
+        return None
+    v = v[lo:hi]
+    return v.repeat(m, *([1] * (v.dim() - 1))) if m > 1 else v
+
+
+def _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol):
+    """A likelihood of parameter sets (ode_vec, nn_flat) x the patients (x0, t, meal, tvns, gd: shared by the sets) and its
+    gradient in one pass over the pieces of `plan` (_plan_sets): forward solve with tape (one tape buffer, handed from piece to
+    piece) -> gy = cotangent(sol, s0, s1, lo, hi), the caller's likelihood of the sets s0..s1-1 x the patients lo..hi-1 at sol.y
+    (it may keep sol's statuses or y) -> adjoint.  -> (gx0 summed over the sets, gnn, gode) where want = (gx0, gnn, gode) asks;
+    with nothing wanted the solves are plain forward solves and `cotangent` only accumulates."""
+    steps, pieces = plan
+    grads, one, n_sets = any(want), len(pieces) == 1, pieces[-1][1]
+    P = hode.n_params(H, L)
+    gx0 = torch.zeros_like(x0) if want[0] else None
+    gnn = nn_flat.new_zeros(n_sets * P) if want[1] and not one else None
+    gode = ode_vec.new_zeros(n_sets * 17) if want[2] and not one else None
+    tape = None
+    for s0, s1, lo, hi in pieces:
+        m = s1 - s0
+        args = (_rep(x0, lo, hi, m), t if t.dim() == 1 else _rep(t, lo, hi, m), _rep(meal, lo, hi, m), _rep(tvns, lo, hi, m),
+                _rep(gd, lo, hi, m), ode_vec[17 * s0:17 * s1], nn_flat[P * s0:P * s1], H, L)
+        if not grads:
+            cotangent(hode.solve_fwd(*args, method=method, rtol=rtol, atol=atol, n_sets=m), s0, s1, lo, hi)
+            continue
+        sol = _solve_taped(*args, method, rtol, atol, m, steps, tape=tape)
+        tape = sol.tape
+        g0, gn, go = sol.backward(cotangent(sol, s0, s1, lo, hi), want_gnn=want[1], want_gode=want[2])
+        if gx0 is not None:
+            gx0[lo:hi] += g0.view(m, hi - lo, 6).sum(0)
+        if one:
+            gnn, gode = gn, go                     # (the whole batch in one launch: the adjoint's buffers ARE the result)
+        else:
+            _add_sets(gnn, gode, s0, s1, gn, go)
+    return gx0, gnn, gode
+
+
 def _gauss_lik_core(need, x0, nn_flat, ode_vec, t, meal, tvns, gd, obs, H, L, method, rtol, atol, S, info, group=None, want_y=False,
                     tape_steps=None, scale=1.0, ss=None):
     """Body of _GaussLikFn.forward (also the data term of _TrainLossFn): sum of squares into `ss` (fp64[1]), gradients of
     scale * sum of squares with respect to (x0, nn_flat, ode_vec) where need[i], trajectories when want_y."""
-    grads = any(need[:3])
-    B, T = x0.shape[0], t.shape[-1]
-    P = nn_flat.numel() // S
-    steps = (_small_tape_steps(S * B, T, method, x0.element_size(), L, H, tape_steps) if grads else None) or _tape_steps(T, method, tape_steps)
-    per_traj = hode.capi.tape_nbytes(1, steps, x0.element_size(), L, H)
-    cap = max(1, _tape_budget(x0.device, S * B * per_traj) // per_traj) if grads else S * B
+    want = tuple(need[:3])
+    grads = any(want)
+    plan = _plan_sets(x0.device, S, x0.shape[0], t.shape[-1], method, x0.element_size(), L, H, tape_steps, grads)
     if ss is None:
         ss = torch.zeros(1, dtype=torch.float64, device=x0.device)
-    pieces = _pieces(S, B, cap)
-    one_piece = len(pieces) == 1
-    gx0 = torch.zeros_like(x0) if need[0] else None
-    gnn = torch.zeros_like(nn_flat) if need[1] and not one_piece else None
-    gode = torch.zeros_like(ode_vec) if need[2] and not one_piece else None
-    tape, stat, nst, nfe, ys, retried, worst = None, [], [], [], [], 0, 0
-    for s0, s1, lo, hi in pieces:
-        m = s1 - s0
-        rep = lambda v: None if v is None else (v[lo:hi].repeat(m, *([1] * (v.dim() - 1))) if m > 1 else v[lo:hi])  # noqa: E731
-        if grads:
-            sol = _solve_taped(rep(x0), t if t.dim() == 1 else rep(t), rep(meal), rep(tvns), rep(gd), ode_vec[17 * s0:17 * s1],
-                               nn_flat[P * s0:P * s1], H, L, method, rtol, atol, m, steps, tape=tape)
-            tape = sol.tape
-            retried += sol.n_retried
-            worst = None if (worst is None or sol.worst is None) else max(worst, sol.worst)
-        else:
-            sol = hode.solve_fwd(rep(x0), t if t.dim() == 1 else rep(t), rep(meal), rep(tvns), rep(gd), ode_vec[17 * s0:17 * s1],
-                                 nn_flat[P * s0:P * s1], H, L, method=method, rtol=rtol, atol=atol, n_sets=m)
-        _, gy = hode.mse_fwd_bwd(sol.y, rep(obs), scale, loss_sum=ss, want_grad=grads)
-        if grads:
-            g0, gn, go = sol.backward(gy, want_gnn=need[1], want_gode=need[2])
-            if gx0 is not None:
-                gx0[lo:hi] += g0.view(m, hi - lo, 6).sum(0)
-            if one_piece:
-                gnn, gode = gn, go                 # (the whole batch in one launch: the adjoint's buffers ARE the result)
-            else:
-                if gn is not None:
-                    gnn[P * s0:P * s1] += gn
-                if go is not None:
-                    gode[17 * s0:17 * s1] += go
-        stat.append(sol.status), nst.append(sol.nsteps), nfe.append(sol.nfev)
-        if want_y:
-            ys.append(sol.y)
-    one = len(stat) == 1
+    sols = []
+
+    def cotangent(sol, s0, s1, lo, hi):
+        sols.append((sol.status, sol.nsteps, sol.nfev, sol.y if want_y else None) + ((sol.n_retried, sol.worst) if grads else (0, None)))
+        return hode.mse_fwd_bwd(sol.y, _rep(obs, lo, hi, s1 - s0), scale, loss_sum=ss, want_grad=grads)[1]
+    gx0, gnn, gode = _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol)
+    stat, nst, nfe, ys, retried, worst = zip(*sols)
+    one = len(sols) == 1
     info["status"], info["nsteps"], info["nfev"] = (stat[0], nst[0], nfe[0]) if one else (torch.cat(stat), torch.cat(nst), torch.cat(nfe))
-    info["n_budget_retries"] = retried
-    if grads and worst is not None:
-        info["worst_status"] = worst          # the host has already looked (one synchronisation per piece): 0 = nothing failed
+    info["n_budget_retries"] = sum(retried)
+    if grads and None not in worst:
+        info["worst_status"] = max(worst)     # the host has already looked (one synchronisation per piece): 0 = nothing failed
     if group is not None:
         # patients sharded over the ranks, the SAME S draws everywhere: one all-reduce(sum) of
         # [per-set MLP grads | per-set ODE grads | sum of squares] makes value and gradient global on every rank
         _allreduce_sum([v for v in (gnn, gode, ss) if v is not None], None if group is True else group)
     y = None
     if want_y:                                     # the trajectories themselves (S = 1), e.g. for the physics points
-        y = ys[0] if len(ys) == 1 else torch.cat(ys)
+        y = ys[0] if one else torch.cat(ys)
     return ss, y, (gx0, gnn, gode)
 
 
@@ -521,6 +561,12 @@ class _TrainLossFn(torch.autograd.Function):
         ctx.grads = None
         sc = lambda v: None if v is None else v.mul_(g.to(v.dtype))        # noqa: E731  (the buffers are this node's own)
         return (sc(gnn), sc(gode)) + (None,) * 15
+
+
+def _device_batch(model, batch, dev, dtype):
+    """(x0, t, meal, tvns, gd) of a batch dict on `dev`, cast to `dtype` and contiguous: what the kernels take."""
+    x0, t, ins = model._prep_inputs(batch["initial_state"], batch["time_points"], batch.get("external_inputs"), dev)
+    return tuple(None if v is None else v.to(dtype).contiguous() for v in (x0, t, ins["meal"], ins["tVNS"], ins["GD"]))
 
 
 class HybridODENN(nn.Module):
@@ -712,9 +758,7 @@ class HybridODENN(nn.Module):
         x0, t, ins = self._prep_inputs(initial_state, t_span, external_inputs, dev)
         if nn_flat is None:
             nn_flat, ode_vec = self._params_on(dev, params)
-        method = _SOLVERS.get(str(solver).lower())
-        if method is None:
-            raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+        method = _method(solver)
         diff = (self.adjoint if differentiable is None else differentiable) and not nn_shared
         info = {}
         nl = self.nn_residual
@@ -931,9 +975,7 @@ class HybridODENN(nn.Module):
                 cols.append(("ode", ODE_PARAM_NAMES.index(key)))
         if not cols:
             raise ValueError("sensitivities needs at least one entry in wrt")
-        method = _SOLVERS.get(str(solver).lower())
-        if method is None:
-            raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+        method = _method(solver)
         nl = self.nn_residual
         H, L = nl.hidden_dim, nl.hip_layers
         with torch.no_grad():
@@ -949,8 +991,7 @@ class HybridODENN(nn.Module):
                     ode_mat[:, ODE_PARAM_NAMES.index(key)] = torch.as_tensor(vals).to(dev, dtype).reshape(-1).expand(B)
                 ode_vec, nn_flat, n_sets = ode_mat.reshape(-1).contiguous(), nn_flat.repeat(B).contiguous(), B
             if max_steps is None:
-                max_steps = (_small_tape_steps(B, T, method, torch.finfo(dtype).bits // 8, L, H, self.tape_steps)
-                             or _tape_steps(T, method, self.tape_steps))
+                max_steps = _taped_steps(B, T, method, torch.finfo(dtype).bits // 8, L, H, self.tape_steps)
             sol = hode.solve_fwd(cast(x0), cast(t), cast(ins["meal"]), cast(ins["tVNS"]), cast(ins["GD"]), ode_vec, nn_flat, H, L,
                                  method=method, rtol=float(rtol), atol=float(atol), max_steps=int(max_steps), n_sets=n_sets,
                                  want_tape=True)
@@ -1002,9 +1043,7 @@ class HybridODENN(nn.Module):
             n_obs = float(cnt)
         log_norm = 0.5 * n_obs * torch.log(torch.tensor(2 * torch.pi * noise_sigma ** 2, dtype=torch.float64, device=dev))
         kl = self.variational_params.kl_divergence().double().to(dev)
-        method = _SOLVERS.get(str(solver).lower())
-        if method is None:
-            raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+        method = _method(solver)
         if self.fused_likelihood and self.adjoint and (torch.is_grad_enabled() or group is not None):
             # data term and its gradient in one pass over the S x B trajectories (_GaussLikFn)
             xs, tt, ins = self._prep_inputs(x0, tp, u, dev)
@@ -1045,19 +1084,17 @@ class HybridODENN(nn.Module):
         from inference.observation import ObservationModel, _ObsNllFn
         self._check_supported()
         dev = _compute_device()
-        method = _SOLVERS.get(str(solver).lower())
-        if method is None:
-            raise ValueError(f"unknown solver {solver!r}; known: {sorted(_SOLVERS)}")
+        method = _method(solver)
         om = ObservationModel() if observation is None else observation
-        x0, t, ins = self._prep_inputs(batch["initial_state"], batch["time_points"], batch.get("external_inputs"), dev)
+        x0, t, meal, tvns, gd = _device_batch(self, batch, dev, dtype)
         if tuple(batch["observations"].shape) != (x0.shape[0], t.shape[-1], 6):
             raise ValueError("observations must be [B, T, 6] on the grid of time_points")
         om.prepare(batch["observations"], batch.get("observation_mask"), dev, dtype)
         nn_flat, ode_vec = self._params_on(dev)
         cast = lambda v: None if v is None else v.to(dtype).contiguous()          # noqa: E731
         info, nl = {}, self.nn_residual
-        y = _SolveFn.apply(cast(x0), cast(nn_flat), cast(ode_vec), cast(t), cast(ins["meal"]), cast(ins["tVNS"]), cast(ins["GD"]),
-                           nl.hidden_dim, nl.hip_layers, method, float(rtol), float(atol), 1, info, self.tape_steps)
+        y = _SolveFn.apply(x0, cast(nn_flat), cast(ode_vec), t, meal, tvns, gd, nl.hidden_dim, nl.hip_layers, method, float(rtol),
+                           float(atol), 1, info, self.tape_steps)
         self.last_solve_info = info
         self._warn_failures(info)
         return _ObsNllFn.apply(y, om)

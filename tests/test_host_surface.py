@@ -66,6 +66,34 @@ def test_argument_validation_without_gpu():
                                   ctypes.c_double(1e-6), ctypes.c_double(1e-8), 100, one, one, z, z, z) == -1  # meal mode w/o ptr
 
 
+@pytest.mark.parametrize("n_sets,G,cap", [(3, 4, 3), (3, 4, 4), (5, 4, 10), (3, 4, 12), (3, 4, 100), (1, 7, 2), (16, 5, 1), (4, 6, 5)])
+def test_sets_plan_covers_every_trajectory_once_within_the_tape_budget(monkeypatch, n_sets, G, cap):
+    """The planning half of the taped-pieces engine alone (no device): n_sets x G trajectories under a budget of `cap` tapes."""
+    import models.hybrid_ode_nn as HN
+    T, H, L, elem, method = 61, 64, 4, 4, hode.METHOD_DP54
+    steps = HN._taped_steps(n_sets * G, T, method, elem, L, H, None)
+    per = hode.capi.tape_nbytes(1, steps, elem, L, H)
+    asked = []
+    monkeypatch.setattr(HN, "_tape_budget", lambda dev, need=0: asked.append(need) or cap * per + per // 2)
+    got_steps, pieces = HN._plan_sets("cpu", n_sets, G, T, method, elem, L, H)
+    assert asked == [n_sets * G * per] and got_steps == steps
+    seen = np.zeros((n_sets, G), dtype=int)
+    for s0, s1, lo, hi in pieces:
+        assert 0 <= s0 < s1 <= n_sets and 0 <= lo < hi <= G
+        seen[s0:s1, lo:hi] += 1
+        assert (s1 - s0) * (hi - lo) <= cap                              # no piece exceeds the budget
+        if cap >= G:
+            assert (lo, hi) == (0, G)                                    # whole sets whenever one fits
+        else:
+            assert s1 - s0 == 1
+    assert (seen == 1).all()                                             # every (set, patient) pair exactly once
+    sizes = [(s1 - s0) * (hi - lo) for s0, s1, lo, hi in pieces]
+    assert sizes[0] == max(sizes)                                        # tape reuse: the first piece's buffer serves the rest
+    assert (len(pieces) == 1) == (cap >= n_sets * G)
+    # nothing to tape without gradients: one piece, and the allocator is not asked
+    assert HN._plan_sets("cpu", n_sets, G, T, method, elem, L, H, grads=False)[1] == [(0, n_sets, 0, G)] and len(asked) == 1
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_hot_path_fails_loudly_without_gpu():
     """No CPU fallback: solve / ode_residual / loss raise when there is no HIP device."""
