@@ -509,10 +509,9 @@ template <bool RELU, bool BIAS> __device__ __forceinline__ float blk_rows_finish
 #ifndef HODE_FINISH_SPLIT
     asm("s_nop 1\n\t"                          /* (hipcc may have just COPIED an accumulator) */
         "v_permlane16_swap_b32 %[a2], %[a3]\n\t" /* a2 = [u2.q0 u3.q0 u2.q2 u3.q2]   a3 = [u2.q1 u3.q1 u2.q3 u3.q3] */
-        "s_nop 0\n\t"
-        "v_permlane16_swap_b32 %[a0], %[a1]"      /* a0 = [u0.q0 u1.q0 u0.q2 u1.q2]   a1 = [u0.q1 u1.q1 u0.q3 u1.q3] */
+        "v_permlane16_swap_b32 %[a0], %[a1]"      /* a0 = [u0.q0 u1.q0 u0.q2 u1.q2]   a1 = [u0.q1 u1.q1 u0.q3 u1.q3]  (three states behind the s_nop's subjects) */
         : [a0] "+v"(a02.x), [a2] "+v"(a02.y), [a1] "+v"(a13.x), [a3] "+v"(a13.y));
-    asm("s_nop 0\n\tv_pk_add_f32 %0, %0, %1" : "+v"(a02) : "v"(a13));     // rows: u0 / u2 q0+q1, u1 / u3 q0+q1, q2+q3, q2+q3
+    asm("v_pk_add_f32 %0, %0, %1" : "+v"(a02) : "v"(a13));     // rows: u0 / u2 q0+q1, u1 / u3 q0+q1, q2+q3, q2+q3
     float a0 = a02.x, a2 = a02.y;
 #else
     // On the four accumulators as FOUR 32-bit operands of one statement (the halves are free to read; as read-write halves of the two
@@ -555,63 +554,85 @@ template <bool RELU, bool BIAS> __device__ __forceinline__ float blk_rows_finish
 // moved operand (op_sel_hi:[1,0,1]) -- 47 instructions per layer instead of 64 v_fmac_f32_dpp, 12.3 against 14.7 SIMD cycles per
 // rotation at two waves per SIMD (tools/ubench/inst_cost_ubench.hip: k_step_pk2 / k_step_dpp4).  Same products, same order per
 // accumulator, one rounding per FMA: bit-identical to the DPP form.
-// One asm statement per instruction group: the moved operand must be an asm OPERAND (a 64-bit pair cannot be named as its low half
-// for the 32-bit v_mov_b32_dpp inside one statement; naming a fixed pair such as v[0:1] and declaring it clobbered was tried: hipcc
-// then spills whatever lived there and reloads it -- with a full vmcnt wait -- inside the stage loop of the taping kernel).  The
-// s_nops hipcc puts between the statements are issue slots of the SIMD's other wave and cost nothing measurable.
+// A rotation's move and its FMAs stand in ONE asm statement.  The moved operand has to be named as a 32-bit register for the
+// v_mov_b32_dpp and as a 64-bit pair for the packed FMAs, which an allocator-chosen operand cannot be; as two statements (the
+// layout of rounds 3-4) hipcc put its boundary pad -- one s_nop behind a statement whose output the next instruction reads --
+// between every move and its FMAs: 245 of the 457 s_nops of the 1 904-instruction DP5(4) step, a quarter of a lone wave's issue
+// slots.  Naming a fixed pair such as v[0:1] and declaring it CLOBBERED had been tried: hipcc then spills whatever lived there and
+// reloads it, with a full vmcnt wait, inside the stage loop of the taping kernel.  A fixed register as an early-clobber OUTPUT is a
+// def the allocator plans around: no fp32 instantiation of the forward, JVP, RHS or adjoint kernels gained scratch, two lost theirs.
+// Measured (profiles/fwd_asm_merge_ab.log, four alternating pairs on one MI355X): step block 1 904 -> 1 569 instructions, s_nop
+// 457 -> 123, vector instructions 1 438 -> 1 437; benchmark launch 2.724 -> 2.655 ms (-2.6 %), taping forward 3.21 -> 3.06 ms (-4.6 %).
+// So the pads were NOT free issue slots of the SIMD's other wave -- and removing 17.6 % of a wave's instructions bought 2.6 %: the
+// vector pipe of a SIMD with two resident waves is what binds, the pads cost where a wave runs alone or both waves stall.
 template <bool RELU> __device__ __forceinline__ float mlp_hidden_blk(const f2_t (&wp)[kMaxH / 2], float bias, float h)
 {
     // accumulator pairs (a0, a2) and (a1, a3): after the two 16-lane swaps the sums a0 + a1 and a2 + a3 are ONE packed add
-    f2_t a02, a13, hr;
-    // h is a FRESH vector result (the previous layer's v_max) and a DPP read needs two wait states behind its producer.  The two
-    // products of rotation 0 used to BE those wait states -- by source order; but a DPP move depends on h only, and in some
-    // instantiations (RK4 x three layers x tape) hipcc scheduled moves in front of the products: stale lanes, trajectories off by
-    // 1e-1, silently (found by tools/soak_tuned.py, pinned down and now checked by tools/dpp_hazard_check.py).  So every reader of h
-    // takes it from this statement: two wait states, one issue slot, and the moves stay free to be scheduled early.
-    asm("s_nop 1" : "+v"(h));
+    f2_t a02, a13;
+    // h is a FRESH vector result (the previous layer's v_max) and a DPP read needs two wait states behind its producer.  By source
+    // order alone that is not safe: a DPP move depends on h only, and when the moves were statements of their own hipcc scheduled
+    // some in front of the rotation-0 products in some instantiations (RK4 x three layers x tape): stale lanes, trajectories off by
+    // 1e-1, silently (found by tools/soak_tuned.py, checked by tools/dpp_hazard_check.py).  Now every DPP read of h is INSIDE a
+    // string, behind at least two instructions of that string that are not DPP reads -- whatever hipcc puts in front of a statement
+    // (a copy of h into its register, say) is two wait states old by then.
 #ifndef HODE_BLK_UNPINNED
     // The accumulators live in v[4:7] BY NAME (constraint {v[..]} on every statement of the layer, so that the register
     // allocator keeps them there from the first product to the last swap): the finish can then swap HALVES of the pairs and add
     // the PAIRS -- 2 swaps + 1 packed add.  With allocator-chosen pairs the halves are separate operands, and hipcc wrapped the
     // swaps of two layers out of three in a copy out of a pair and back (5 instructions; tools/fwd_valu.py).  Kernels that hold
     // the weights in registers run at two waves per SIMD (256 registers), so v4..255 exist wherever this function is used.
-#define HODE_A02 "+{v[4:5]}"(a02)
-#define HODE_A13 "+{v[6:7]}"(a13)
-    {
-        f2_t hh;
-        hh.x = h;
-        asm("v_pk_mul_f32 v[4:5], %2, %4 op_sel_hi:[1,0]\n\tv_pk_mul_f32 v[6:7], %3, %4 op_sel_hi:[1,0]"
-            : "=&{v[4:5]}"(a02), "=&{v[6:7]}"(a13) : "v"(wp[0]), "v"(wp[1]), "v"(hh));
-    }
-#define HODE_BK_STEP(n)                                                                                                        \
-    {                                                                                                                          \
-        float lo;                                                                                                              \
-        asm("v_mov_b32_dpp %0, %1 row_ror:" #n " row_mask:0xf bank_mask:0xf" : "=v"(lo) : "v"(h));                             \
-        hr.x = lo;                                                                                                             \
-        asm("v_pk_fma_f32 v[4:5], %2, %4, v[4:5] op_sel_hi:[1,0,1]\n\tv_pk_fma_f32 v[6:7], %3, %4, v[6:7] op_sel_hi:[1,0,1]" \
-            : HODE_A02, HODE_A13 : "v"(wp[2 * n]), "v"(wp[2 * n + 1]), "v"(hr));                                               \
-    }
-    HODE_BK_STEP(1) HODE_BK_STEP(2) HODE_BK_STEP(3) HODE_BK_STEP(4) HODE_BK_STEP(5) HODE_BK_STEP(6) HODE_BK_STEP(7) HODE_BK_STEP(8)
-    HODE_BK_STEP(9) HODE_BK_STEP(10) HODE_BK_STEP(11) HODE_BK_STEP(12) HODE_BK_STEP(13) HODE_BK_STEP(14) HODE_BK_STEP(15)
-#undef HODE_BK_STEP
-    // a02 = v4 (a0), v5 (a2); a13 = v6 (a1), v7 (a3).  Same sums as blk_rows_finish: (q0 + q1) + (q2 + q3) + b
+    // The moved operand of a rotation is v8 BY NAME as well: the 32-bit v_mov_b32_dpp writes v8 and the packed FMAs read the pair
+    // v[8:9], of which op_sel_hi:[1,0,1] selects the low half twice -- v9 is read and never used, whatever lives there.  The layer's
+    // input sits in v[10:11], so that one register is the 32-bit source of the moves (v10) and the pair of the rotation-0 products.
+    // A statement takes 30 operands, so the layer is two: rotations 0..7 + the move of rotation 8, then the FMAs of rotation 8,
+    // rotations 9..15 and the finish.  The second statement so opens with two plain FMAs, not with a DPP read of v10 (hipcc did
+    // reload v10 right in front of it in rhs_bwd_kernel<float, 4>); the one boundary pad of the layer falls between that move and
+    // its FMAs.
+    f2_t hh;
+    float lo;
+    hh.x = h;
+#define HODE_BK_MOV(n) "v_mov_b32_dpp v8, v10 row_ror:" #n " row_mask:0xf bank_mask:0xf\n\t"
+#define HODE_BK_FMA(n)                                                                                                         \
+    "v_pk_fma_f32 v[4:5], %[wa" #n "], v[8:9], v[4:5] op_sel_hi:[1,0,1]\n\t"                                                    \
+    "v_pk_fma_f32 v[6:7], %[wb" #n "], v[8:9], v[6:7] op_sel_hi:[1,0,1]\n\t"
+#define HODE_BK_STEP(n) HODE_BK_MOV(n) HODE_BK_FMA(n)
+#define HODE_BK_W(n) [wa##n] "v"(wp[2 * n]), [wb##n] "v"(wp[2 * n + 1])
+    // (the s_nop 1 predates the merge: with the two products in front of the first move it is one wait state more than needed)
     asm("s_nop 1\n\t"
-        "v_permlane16_swap_b32 v5, v7\n\t"   /* a2 = [u2.q0 u3.q0 u2.q2 u3.q2]   a3 = [u2.q1 u3.q1 u2.q3 u3.q3] */
-        "s_nop 0\n\t"
-        "v_permlane16_swap_b32 v4, v6\n\t"   /* a0 = [u0.q0 u1.q0 u0.q2 u1.q2]   a1 = [u0.q1 u1.q1 u0.q3 u1.q3] */
-        "s_nop 0\n\t"
-        "v_pk_add_f32 v[4:5], v[4:5], v[6:7]\n\t"     /* rows: u0 / u2 q0+q1, u1 / u3 q0+q1, q2+q3, q2+q3 */
-        "s_nop 1\n\t"
-        "v_permlane32_swap_b32 v4, v5\n\t"
-        "v_add_f32 v4, v4, v5\n\t"
-        "v_add_f32 v4, v4, %[bias]"
-        : HODE_A02, HODE_A13 : [bias] "v"(bias));
-#undef HODE_A02
-#undef HODE_A13
-    float r = a02.x;
-    if constexpr (RELU) asm("v_max_f32 %0, 0, %0" : "+v"(r));
-    return r;
+        "v_pk_mul_f32 v[4:5], %[wa0], v[10:11] op_sel_hi:[1,0]\n\t"
+        "v_pk_mul_f32 v[6:7], %[wb0], v[10:11] op_sel_hi:[1,0]\n\t"
+        HODE_BK_STEP(1) HODE_BK_STEP(2) HODE_BK_STEP(3) HODE_BK_STEP(4) HODE_BK_STEP(5) HODE_BK_STEP(6) HODE_BK_STEP(7) HODE_BK_MOV(8)
+        : "=&{v[4:5]}"(a02), "=&{v[6:7]}"(a13), "=&{v8}"(lo)
+        : "{v[10:11]}"(hh), HODE_BK_W(0), HODE_BK_W(1), HODE_BK_W(2), HODE_BK_W(3), HODE_BK_W(4), HODE_BK_W(5), HODE_BK_W(6),
+          HODE_BK_W(7));
+    // a02 = v4 (a0), v5 (a2); a13 = v6 (a1), v7 (a3).  Same sums as blk_rows_finish: (q0 + q1) + (q2 + q3) + b.  Pads: a lane swap
+    // reads its operands through the cross-lane path, two wait states behind the VALU that wrote them -- v7 (the last FMA) and
+    // v[4:5] (the packed add); the second 16-lane swap reads v4 / v6, which are older, and a plain VALU reads a swap's result at once.
+#define HODE_BK_TAIL(RELU_TAIL)                                                                                                \
+    asm(HODE_BK_FMA(8) HODE_BK_STEP(9) HODE_BK_STEP(10) HODE_BK_STEP(11) HODE_BK_STEP(12) HODE_BK_STEP(13) HODE_BK_STEP(14)   \
+        HODE_BK_STEP(15)                                                                                                       \
+        "s_nop 1\n\t"                                                                                                          \
+        "v_permlane16_swap_b32 v5, v7\n\t"   /* a2 = [u2.q0 u3.q0 u2.q2 u3.q2]   a3 = [u2.q1 u3.q1 u2.q3 u3.q3] */             \
+        "v_permlane16_swap_b32 v4, v6\n\t"   /* a0 = [u0.q0 u1.q0 u0.q2 u1.q2]   a1 = [u0.q1 u1.q1 u0.q3 u1.q3] */             \
+        "v_pk_add_f32 v[4:5], v[4:5], v[6:7]\n\t"     /* rows: u0 / u2 q0+q1, u1 / u3 q0+q1, q2+q3, q2+q3 */                   \
+        "s_nop 1\n\t"                                                                                                          \
+        "v_permlane32_swap_b32 v4, v5\n\t"                                                                                     \
+        "v_add_f32 v4, v4, v5\n\t"                                                                                             \
+        "v_add_f32 v4, v4, %[bias]" RELU_TAIL                                                                                  \
+        : "+{v[4:5]}"(a02), "+{v[6:7]}"(a13), "+{v8}"(lo)                                                                      \
+        : "{v[10:11]}"(hh), [bias] "v"(bias), HODE_BK_W(8), HODE_BK_W(9), HODE_BK_W(10), HODE_BK_W(11), HODE_BK_W(12),         \
+          HODE_BK_W(13), HODE_BK_W(14), HODE_BK_W(15))
+    if constexpr (RELU) HODE_BK_TAIL("\n\tv_max_f32 v4, 0, v4");
+    else HODE_BK_TAIL("");
+#undef HODE_BK_TAIL
+#undef HODE_BK_W
+#undef HODE_BK_STEP
+#undef HODE_BK_FMA
+#undef HODE_BK_MOV
+    return a02.x;
 #else
+    f2_t hr;
+    asm("s_nop 1" : "+v"(h));
     // n = 0: the lane's own activation (no rotation); plain products start the sums (h is a fresh VALU result: these two
     // instructions are also the wait states its first DPP read needs)
     {
