@@ -21,6 +21,8 @@ namespace hode {
 // (group j), the multinomial choice of leaf n (group n, counted over the tree from 1), the merge of subtree j (group j)
 constexpr uint32_t kRngMomentum = 0, kRngAccept = 1, kRngJitter = 2, kRngInit = 3;
 constexpr uint32_t kRngNutsDir = 4, kRngNutsLeaf = 5, kRngNutsMerge = 6;
+// the bootstrap of the Sobol indices (hode_sobol.hip): resample r as the iteration, base sample q / 4 as the group, chain 0
+constexpr uint32_t kRngSobol = 7;
 
 struct Philox4 { uint32_t x, y, z, w; };
 

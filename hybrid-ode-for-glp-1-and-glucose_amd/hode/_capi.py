@@ -28,7 +28,7 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_solve_jvp_f32", "hode_solve_jvp_f64",
            "hode_nuts_begin_f32", "hode_nuts_begin_f64", "hode_nuts_pre_f32", "hode_nuts_pre_f64", "hode_nuts_post_f32",
            "hode_nuts_post_f64", "hode_nuts_compact", "hode_nuts_finish_f32", "hode_nuts_finish_f64",
-           "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64"]
+           "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64", "hode_sobol_indices_f32", "hode_sobol_indices_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -408,6 +408,38 @@ def obs_nll_sets(y, obs, mask, mode, sse, loss_sum=None, w=None, a=None, b=None,
                                                                _ptr(mask), C.c_int(mode), C.c_int(flags), _six(w), _six(a), _six(b),
                                                                _six(n), _ptr(sse), _ptr(loss_sum), _ptr(gy)), "hode_obs_nll_sets")
     return gy
+
+
+SOBOL_MAX_D = 32
+
+
+def sobol_indices(Y, D, second_order=True, R=100, seed=0, conf_z=1.959963984540054):
+    """Sobol indices of the outputs of a Saltelli design (include/hode.h "Sobol indices"): Y [N * nb, M] on the device, fp32 or
+    fp64, nb = 2 D + 2 with second_order and D + 2 without, row i * nb + b = block b (A, AB_1..AB_D, [BA_1..BA_D,] B) of base
+    sample i; the rows may be strided (Y.stride(0) >= M, unit stride along the columns), so a slice of columns goes in as it is.
+    R bootstrap resamples (Philox stream 7 of `seed`), conf = conf_z * their ddof-1 standard deviation.  Returns a dict of fp64
+    device tensors: S1, ST, S1_conf, ST_conf [M, D]; S2, S2_conf [M, D, D] (None without second_order; NaN off the pairs
+    j < k); variance [M].  The conf entries are NaN for R < 2."""
+    _need_gpu(Y)
+    if Y.dim() != 2 or Y.shape[1] < 1:
+        raise HodeError("sobol_indices: Y must be [rows, M] with M >= 1")
+    if Y.stride(1) != 1 or Y.stride(0) < Y.shape[1]:
+        Y = Y.contiguous()
+    nb = 2 * D + 2 if second_order else D + 2
+    rows, M = Y.shape
+    if D > SOBOL_MAX_D:
+        raise HodeError(f"sobol_indices: D = {D} parameters, the kernel takes up to {SOBOL_MAX_D} (HODE_SOBOL_MAX_D)")
+    if D < 1 or rows < nb or rows % nb:
+        raise HodeError(f"sobol_indices: {rows} rows are not a positive multiple of the {nb} blocks of a design in D = {D}")
+    dev = Y.device
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)                     # noqa: E731
+    out = {"S1": new(M, D), "ST": new(M, D), "S2": new(M, D, D) if second_order else None,
+           "S1_conf": new(M, D), "ST_conf": new(M, D), "S2_conf": new(M, D, D) if second_order else None, "variance": new(M)}
+    _check(getattr(load(), f"hode_sobol_indices_{_sfx(Y.dtype)}")(
+        _stream(), C.c_int(rows // nb), C.c_int(D), C.c_int(M), _ptr(Y), C.c_int64(Y.stride(0)), C.c_int(int(bool(second_order))),
+        C.c_int(int(R)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_double(conf_z), _ptr(out["S1"]), _ptr(out["ST"]), _ptr(out["S2"]),
+        _ptr(out["S1_conf"]), _ptr(out["ST_conf"]), _ptr(out["S2_conf"]), _ptr(out["variance"])), "hode_sobol_indices")
+    return out
 
 
 def hmc_refresh(C_, D, ld, seed, it, jitter, minv, log_eps, z, g, U, p, z0, g0, U0, ke0, eps, failed):

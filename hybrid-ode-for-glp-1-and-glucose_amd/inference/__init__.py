@@ -20,9 +20,11 @@ import os
 import sys
 
 from .calibrate import CalibrationResult, fit_patients
+from .sobol import SobolIndices, saltelli_design, sobol_indices, sobol_study
 from .vi import VariationalInference
 
-__all__ = ["VariationalInference", "fit_patients", "CalibrationResult", "run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results"]
+__all__ = ["VariationalInference", "fit_patients", "CalibrationResult", "run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results",
+           "sobol_study", "sobol_indices", "saltelli_design", "SobolIndices"]
 
 _MCMC_NAMES = ("run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results")
 _HERE = os.path.dirname(os.path.abspath(__file__))

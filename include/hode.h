@@ -478,6 +478,46 @@ int hode_nuts_finish_f64(void *stream, int C, int D, int ld, int adapt, double t
                          const double *tree, const double *dst, const int32_t *ist, double *log_eps, double *da, int n_ode,
                          const double *mu, const double *sd, double *draws, double *stats, int n_slots, int slot);
 
+/* =====================================================================================================
+ * Sobol indices (inference/sobol.py, sobol_indices / sobol_study): the analysis half of the sensitivity study of the
+ * reference's plots/plot_all.py:139-224, i.e. what SALib.analyze.sobol.analyze computes from the model outputs of a
+ * Saltelli design, for M output columns at once.
+ *
+ * Input.  Y holds N * nb rows, nb = 2 D + 2 with second_order and D + 2 without; row i * nb + b is block b of base sample i,
+ * the blocks in SALib's order A, AB_1..AB_D, [BA_1..BA_D,] B.  Element (row, m) is Y[row * ldy + m], ldy >= M: trajectories
+ * y[S][T][6] go in as they are with M = ldy = 6 T.  DEVICE memory, any alignment, any ldy.
+ *
+ * Estimators, per column m.  z = (Y - mean) / std with mean and std (ddof 0) over all N * nb rows of the column;
+ * V = the ddof-0 variance of the 2 N values A u B;
+ *   S1_j  = mean_i(B_i (AB_ij - A_i)) / V
+ *   ST_j  = mean_i((A_i - AB_ij)^2) / (2 V)
+ *   S2_jk = mean_i(BA_ij AB_ik - A_i B_i) / V - S1_j - S1_k    for j < k; every other entry of S2 is NaN.
+ * Confidence: resample r < R draws indices rho_r(q), q < N, and applies the same formulas to A[rho], AB[rho], BA[rho], B[rho]
+ * (V again from the resampled A u B); *_conf = conf_z * the ddof-1 standard deviation of the R resampled estimates, NaN for
+ * R < 2.  rho_r(q) = (word * N) >> 32 with word = element q & 3 of the Philox4x32-10 block of counter (q >> 2, 7, r,
+ * seed bits 32..63) and key (seed bits 0..31, 0): stream tag 7 of the samplers' generator.  All columns share rho; it depends
+ * on (seed, r, q, N) only.
+ *
+ * Outputs (DEVICE, fp64): S1, ST [M][D]; S2 [M][D][D] (read only with second_order); S1_conf, ST_conf, S2_conf the same shapes
+ * (all may be NULL when R == 0); variance [M] = the ddof-0 variance of the raw column over all rows (may be NULL).
+ * A column whose raw values are all equal, or that holds a non-finite value, gets NaN in every index and conf and variance 0
+ * or NaN; its neighbours are not disturbed.
+ *
+ * Arithmetic: inputs converted to fp64 on load, every sum fp64 in a fixed order, no floating-point atomics.  One workgroup
+ * per column; the column is staged in LDS when it fits and gathered from global memory when not, with the same bits either
+ * way.  The same call gives the same bits, and a call on M columns gives the bits of M one-column calls.
+ *
+ * HODE_EINVAL: N, D or M < 1, ldy < M, R < 0, a NULL among Y, S1, ST, S2 NULL with second_order, a NULL conf with R > 0 whose
+ * index array is given.  HODE_EUNSUPPORTED: D > HODE_SOBOL_MAX_D.
+ * ===================================================================================================== */
+#define HODE_SOBOL_MAX_D 32
+int hode_sobol_indices_f32(void *stream, int N, int D, int M, const float *Y, int64_t ldy, int second_order, int R, uint64_t seed,
+                           double conf_z, double *S1, double *ST, double *S2, double *S1_conf, double *ST_conf, double *S2_conf,
+                           double *variance);
+int hode_sobol_indices_f64(void *stream, int N, int D, int M, const double *Y, int64_t ldy, int second_order, int R, uint64_t seed,
+                           double conf_z, double *S1, double *ST, double *S2, double *S1_conf, double *ST_conf, double *S2_conf,
+                           double *variance);
+
 #ifdef __cplusplus
 }
 #endif
