@@ -654,6 +654,168 @@ template <bool RELU> __device__ __forceinline__ float mlp_hidden_blk(const f2_t 
     return blk_rows_finish<RELU, true>(a02, a13, bias);
 #endif
 }
+// ---- the same layer with its LAST K rotations fetched through LDS (forward solve kernels only) --------------------------------
+// The 15 v_mov_b32_dpp of mlp_hidden_blk are copies on the pipe that binds the forward kernel.  Here the wave writes the layer's
+// input to a private LDS buffer of 4 rows x 48 dwords (kRotBufElems; row r holds its 16 activations twice, at entries j and
+// j + 16: ONE ds_write2_b32) and fetches the moved operands of rotations 16 - K .. 15 at the layer's START, two per
+// ds_read2_b32 into an aligned register pair: lane (r, i) reads rotation n at entry i + 16 - n of row r, immediate offsets on
+// the one per-lane address `rot` (rot_lane_addr).  Rotations 0 .. 15 - K stay DPP and hide the round trip; one
+// s_waitcnt lgkmcnt(0); then the packed FMAs of rotation n take the pair's low half (op_sel_hi:[1,0,1], as with v[8:9]) and
+// those of n + 1 its high half (op_sel:[0,1,0] op_sel_hi:[1,1,1]).  Same products, same weight pairs, same order per
+// accumulator, same finish: the bits of mlp_hidden_blk.
+// Row stride 48: inside each 32-lane group rows 0/1 and 2/3 fall on disjoint halves of the 32 banks -- no conflict, write or read.
+// The wait is lgkmcnt(0): the scalar look-ahead loads of UniformInput share the counter and return out of order (they were
+// issued an interval earlier).  It stands at the END of the first statement, so every fetched pair is complete before hipcc
+// sees it as a value it may copy; DS operations of one wave execute in order, so nothing stands between the write and the
+// reads, and the buffer is private to the wave (one wave per workgroup): no barrier.
+// Registers: K / 2 pairs and the address, live through the layer.  LEAN (K = 8) lands the first two LDS rotations in v9 and
+// v11 instead -- the high halves of the moved-operand pair and of the input pair, which the DPP part never selects -- by two
+// ds_read_b32 (the LDS cycles of one ds_read2_b32): K = 8 for 8 registers, not 9, which is what the benchmark kernel has.
+// Which instantiation takes which K: FwdRot, hode_solve_fwd.hip.
+// Measured (tools/ubench/fwd_lds_rot_ubench.hip, profiles/fwd_lds_rot_ubench.log): chain form, cycles per layer and SIMD,
+// K = 0 / 4 / 8 / lean 8 / 12: 285.7 / 287.5 / 282.1 / 279.3 / 271.4 at two waves per SIMD, 425.5 / 445.2 / 442.7 / 446.2 / 430.0 at
+// one -- a wave that has its SIMD to itself pays for the round trip; a pair fetched a second time behind its first use (fewer registers) loses at
+// both.  In the kernels (profiles/fwd_lds_rot_ab.log): benchmark launch 2.618 -> 2.547 ms (-2.7 %) with the lean K = 8, three
+// layers 2.04 -> 1.96 ms with K = 12; launches of at most one wave per SIMD (B <= 1 024) +3.4 .. +4.5 %.
+constexpr int kRotBufElems = 4 * 48;
+// byte address of entry i of row r in the wave's buffer at LDS byte offset `base`
+__device__ __forceinline__ unsigned rot_lane_addr(unsigned base, int lane) { return base + 4u * (48 * (lane >> 4) + (lane & 15)); }
+template <bool RELU, int K, bool LEAN = false>
+__device__ __forceinline__ float mlp_hidden_blk_lds(const f2_t (&wp)[kMaxH / 2], float bias, float h, unsigned rot)
+{
+    static_assert(K == 4 || K == 8 || K == 12, "K rotations through LDS: 4, 8 or 12 (0 is mlp_hidden_blk)");
+    static_assert(!LEAN || K == 8, "the lean form exists for K = 8");
+    f2_t a02, a13, hh;
+    float lo;
+    hh.x = h;
+#define HODE_BL_MOV(n) "v_mov_b32_dpp v8, v10 row_ror:" #n " row_mask:0xf bank_mask:0xf\n\t"
+#define HODE_BL_FMA(n)                                                                                                         \
+    "v_pk_fma_f32 v[4:5], %[wa" #n "], v[8:9], v[4:5] op_sel_hi:[1,0,1]\n\t"                                                    \
+    "v_pk_fma_f32 v[6:7], %[wb" #n "], v[8:9], v[6:7] op_sel_hi:[1,0,1]\n\t"
+#define HODE_BL_STEP(n) HODE_BL_MOV(n) HODE_BL_FMA(n)
+    // rotation n from the low half of the fetched pair q, rotation m = n + 1 from its high half
+#define HODE_BL_LDS2(n, m, q)                                                                                                  \
+    "v_pk_fma_f32 v[4:5], %[wa" #n "], %[" #q "], v[4:5] op_sel_hi:[1,0,1]\n\t"                                                 \
+    "v_pk_fma_f32 v[6:7], %[wb" #n "], %[" #q "], v[6:7] op_sel_hi:[1,0,1]\n\t"                                                 \
+    "v_pk_fma_f32 v[4:5], %[wa" #m "], %[" #q "], v[4:5] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"                                  \
+    "v_pk_fma_f32 v[6:7], %[wb" #m "], %[" #q "], v[6:7] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+#define HODE_BL_WR "ds_write2_b32 %[ad], v10, v10 offset1:16\n\t"
+#define HODE_BL_RD(q, o0, o1) "ds_read2_b32 %[" #q "], %[ad] offset0:" #o0 " offset1:" #o1 "\n\t"
+#define HODE_BL_WAIT "s_waitcnt lgkmcnt(0)\n\t"
+    // (two plain products stand between the layer's producer and the first DPP read of v10, as in mlp_hidden_blk)
+#define HODE_BL_HEAD                                                                                                           \
+    "s_nop 1\n\t"                                                                                                              \
+    "v_pk_mul_f32 v[4:5], %[wa0], v[10:11] op_sel_hi:[1,0]\n\t"                                                                \
+    "v_pk_mul_f32 v[6:7], %[wb0], v[10:11] op_sel_hi:[1,0]\n\t"
+#define HODE_BL_FINISH                                                                                                         \
+    "s_nop 1\n\t"                                                                                                              \
+    "v_permlane16_swap_b32 v5, v7\n\t"                                                                                         \
+    "v_permlane16_swap_b32 v4, v6\n\t"                                                                                         \
+    "v_pk_add_f32 v[4:5], v[4:5], v[6:7]\n\t"                                                                                  \
+    "s_nop 1\n\t"                                                                                                              \
+    "v_permlane32_swap_b32 v4, v5\n\t"                                                                                         \
+    "v_add_f32 v4, v4, v5\n\t"                                                                                                 \
+    "v_add_f32 v4, v4, %[bias]"
+#define HODE_BL_W(n) [wa##n] "v"(wp[2 * n]), [wb##n] "v"(wp[2 * n + 1])
+#define HODE_BL_OUT1 "=&{v[4:5]}"(a02), "=&{v[6:7]}"(a13), "=&{v8}"(lo)
+#define HODE_BL_IO2 "+{v[4:5]}"(a02), "+{v[6:7]}"(a13), "+{v8}"(lo)
+#define HODE_BL_IN1 "{v[10:11]}"(hh), [ad] "v"(rot)
+#define HODE_BL_IN2 "{v[10:11]}"(hh), [bias] "v"(bias)
+#define HODE_BL_Q(q) [q] "=&v"(q)
+#define HODE_BL_QI(q) [q] "v"(q)
+    // one rotation from the HIGH half of the named pair p (v[8:9] or v[10:11]: the lean form fetches into v9 and v11)
+#define HODE_BL_HI(n, p)                                                                                                       \
+    "v_pk_fma_f32 v[4:5], %[wa" #n "], " p ", v[4:5] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"                                      \
+    "v_pk_fma_f32 v[6:7], %[wb" #n "], " p ", v[6:7] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+    if constexpr (LEAN) {
+        // The first two LDS rotations land in v9 and v11, the high halves of the moved-operand pair and of the input pair that no
+        // instruction of the DPP part uses (both forms read their low halves only): two rotations for ONE more register (v9; v11
+        // is the input pair's own), each by a ds_read_b32 -- 2 + 2 LDS cycles, what one ds_read2_b32 costs.
+        f2_t lo2, q0, q1, q2;
+        asm(HODE_BL_WR "ds_read_b32 v9, %[ad] offset:32\n\tds_read_b32 v11, %[ad] offset:28\n\t" HODE_BL_RD(q0, 6, 5) HODE_BL_RD(q1, 4, 3)
+            HODE_BL_RD(q2, 2, 1) HODE_BL_HEAD HODE_BL_STEP(1) HODE_BL_STEP(2) HODE_BL_STEP(3) HODE_BL_STEP(4) HODE_BL_STEP(5) HODE_BL_STEP(6)
+            HODE_BL_STEP(7) HODE_BL_WAIT
+            : "=&{v[4:5]}"(a02), "=&{v[6:7]}"(a13), "=&{v[8:9]}"(lo2), "+{v[10:11]}"(hh), HODE_BL_Q(q0), HODE_BL_Q(q1), HODE_BL_Q(q2)
+            : [ad] "v"(rot), HODE_BL_W(0), HODE_BL_W(1), HODE_BL_W(2), HODE_BL_W(3), HODE_BL_W(4), HODE_BL_W(5), HODE_BL_W(6), HODE_BL_W(7));
+#define HODE_BL_TAIL(RELU_TAIL)                                                                                                \
+        asm(HODE_BL_HI(8, "v[8:9]") HODE_BL_HI(9, "v[10:11]") HODE_BL_LDS2(10, 11, q0) HODE_BL_LDS2(12, 13, q1) HODE_BL_LDS2(14, 15, q2) \
+            HODE_BL_FINISH RELU_TAIL                                                                                        \
+            : "+{v[4:5]}"(a02), "+{v[6:7]}"(a13)                                                                            \
+            : "{v[8:9]}"(lo2), "{v[10:11]}"(hh), [bias] "v"(bias), HODE_BL_QI(q0), HODE_BL_QI(q1), HODE_BL_QI(q2), HODE_BL_W(8),      \
+              HODE_BL_W(9), HODE_BL_W(10), HODE_BL_W(11), HODE_BL_W(12), HODE_BL_W(13), HODE_BL_W(14), HODE_BL_W(15))
+        if constexpr (RELU) HODE_BL_TAIL("\n\tv_max_f32 v4, 0, v4");
+        else HODE_BL_TAIL("");
+#undef HODE_BL_TAIL
+    } else if constexpr (K == 4) {
+        f2_t q0, q1;
+        asm(HODE_BL_WR HODE_BL_RD(q0, 4, 3) HODE_BL_RD(q1, 2, 1) HODE_BL_HEAD
+            HODE_BL_STEP(1) HODE_BL_STEP(2) HODE_BL_STEP(3) HODE_BL_STEP(4) HODE_BL_STEP(5) HODE_BL_STEP(6) HODE_BL_STEP(7) HODE_BL_STEP(8)
+            HODE_BL_STEP(9) HODE_BL_STEP(10) HODE_BL_MOV(11) HODE_BL_WAIT
+            : HODE_BL_OUT1, HODE_BL_Q(q0), HODE_BL_Q(q1)
+            : HODE_BL_IN1, HODE_BL_W(0), HODE_BL_W(1), HODE_BL_W(2), HODE_BL_W(3), HODE_BL_W(4), HODE_BL_W(5), HODE_BL_W(6), HODE_BL_W(7),
+              HODE_BL_W(8), HODE_BL_W(9), HODE_BL_W(10));
+#define HODE_BL_TAIL(RELU_TAIL)                                                                                                \
+        asm(HODE_BL_FMA(11) HODE_BL_LDS2(12, 13, q0) HODE_BL_LDS2(14, 15, q1) HODE_BL_FINISH RELU_TAIL                         \
+            : HODE_BL_IO2                                                                                                      \
+            : HODE_BL_IN2, HODE_BL_QI(q0), HODE_BL_QI(q1), HODE_BL_W(11), HODE_BL_W(12), HODE_BL_W(13), HODE_BL_W(14), HODE_BL_W(15))
+        if constexpr (RELU) HODE_BL_TAIL("\n\tv_max_f32 v4, 0, v4");
+        else HODE_BL_TAIL("");
+#undef HODE_BL_TAIL
+    } else if constexpr (K == 8) {
+        f2_t q0, q1, q2, q3;
+        asm(HODE_BL_WR HODE_BL_RD(q0, 8, 7) HODE_BL_RD(q1, 6, 5) HODE_BL_RD(q2, 4, 3) HODE_BL_RD(q3, 2, 1) HODE_BL_HEAD
+            HODE_BL_STEP(1) HODE_BL_STEP(2) HODE_BL_STEP(3) HODE_BL_STEP(4) HODE_BL_STEP(5) HODE_BL_STEP(6) HODE_BL_STEP(7) HODE_BL_WAIT
+            : HODE_BL_OUT1, HODE_BL_Q(q0), HODE_BL_Q(q1), HODE_BL_Q(q2), HODE_BL_Q(q3)
+            : HODE_BL_IN1, HODE_BL_W(0), HODE_BL_W(1), HODE_BL_W(2), HODE_BL_W(3), HODE_BL_W(4), HODE_BL_W(5), HODE_BL_W(6), HODE_BL_W(7));
+#define HODE_BL_TAIL(RELU_TAIL)                                                                                                \
+        asm(HODE_BL_LDS2(8, 9, q0) HODE_BL_LDS2(10, 11, q1) HODE_BL_LDS2(12, 13, q2) HODE_BL_LDS2(14, 15, q3) HODE_BL_FINISH RELU_TAIL \
+            : HODE_BL_IO2                                                                                                      \
+            : HODE_BL_IN2, HODE_BL_QI(q0), HODE_BL_QI(q1), HODE_BL_QI(q2), HODE_BL_QI(q3), HODE_BL_W(8), HODE_BL_W(9), HODE_BL_W(10),  \
+              HODE_BL_W(11), HODE_BL_W(12), HODE_BL_W(13), HODE_BL_W(14), HODE_BL_W(15))
+        if constexpr (RELU) HODE_BL_TAIL("\n\tv_max_f32 v4, 0, v4");
+        else HODE_BL_TAIL("");
+#undef HODE_BL_TAIL
+    } else {
+        f2_t q0, q1, q2, q3, q4, q5;
+        asm(HODE_BL_WR HODE_BL_RD(q0, 12, 11) HODE_BL_RD(q1, 10, 9) HODE_BL_RD(q2, 8, 7) HODE_BL_RD(q3, 6, 5) HODE_BL_RD(q4, 4, 3)
+            HODE_BL_RD(q5, 2, 1) HODE_BL_HEAD HODE_BL_STEP(1) HODE_BL_STEP(2) HODE_BL_STEP(3) HODE_BL_WAIT
+            HODE_BL_LDS2(4, 5, q0) HODE_BL_LDS2(6, 7, q1)
+            : HODE_BL_OUT1, HODE_BL_Q(q0), HODE_BL_Q(q1), HODE_BL_Q(q2), HODE_BL_Q(q3), HODE_BL_Q(q4), HODE_BL_Q(q5)
+            : HODE_BL_IN1, HODE_BL_W(0), HODE_BL_W(1), HODE_BL_W(2), HODE_BL_W(3), HODE_BL_W(4), HODE_BL_W(5), HODE_BL_W(6), HODE_BL_W(7));
+#define HODE_BL_TAIL(RELU_TAIL)                                                                                                \
+        asm(HODE_BL_LDS2(8, 9, q2) HODE_BL_LDS2(10, 11, q3) HODE_BL_LDS2(12, 13, q4) HODE_BL_LDS2(14, 15, q5) HODE_BL_FINISH RELU_TAIL \
+            : HODE_BL_IO2                                                                                                      \
+            : HODE_BL_IN2, HODE_BL_QI(q2), HODE_BL_QI(q3), HODE_BL_QI(q4), HODE_BL_QI(q5), HODE_BL_W(8), HODE_BL_W(9), HODE_BL_W(10),  \
+              HODE_BL_W(11), HODE_BL_W(12), HODE_BL_W(13), HODE_BL_W(14), HODE_BL_W(15))
+        if constexpr (RELU) HODE_BL_TAIL("\n\tv_max_f32 v4, 0, v4");
+        else HODE_BL_TAIL("");
+#undef HODE_BL_TAIL
+    }
+#undef HODE_BL_HI
+#undef HODE_BL_QI
+#undef HODE_BL_Q
+#undef HODE_BL_IN2
+#undef HODE_BL_IN1
+#undef HODE_BL_IO2
+#undef HODE_BL_OUT1
+#undef HODE_BL_W
+#undef HODE_BL_FINISH
+#undef HODE_BL_HEAD
+#undef HODE_BL_WAIT
+#undef HODE_BL_RD
+#undef HODE_BL_WR
+#undef HODE_BL_LDS2
+#undef HODE_BL_STEP
+#undef HODE_BL_FMA
+#undef HODE_BL_MOV
+    return a02.x;
+}
+// The forward solve kernels' weight holder: MlpRegs whose hidden layers take the hybrid form (mlp_load and RhsRegs see an MlpRegs)
+template <int NL, int K, bool LEAN = false> struct MlpRegsRot : MlpRegs<float, NL> {
+    unsigned rot;                     // rot_lane_addr of the wave's buffer
+    __device__ __forceinline__ float hidden(int l, float h) const { return mlp_hidden_blk_lds<false, K, LEAN>(this->wh[l], this->b[l + 1], h, rot); }
+    __device__ __forceinline__ float hidden_relu(int l, float h) const { return mlp_hidden_blk_lds<true, K, LEAN>(this->wh[l], this->b[l + 1], h, rot); }
+};
 // acc[q] += sum_n row_ror:n(R[q]) * w[16 q + n], n ascending within each accumulator; R[] must be two wait states old
 __device__ __forceinline__ void rot_matvec64(const float (&w)[kMaxH], const float (&R)[4], float (&acc)[4])
 {

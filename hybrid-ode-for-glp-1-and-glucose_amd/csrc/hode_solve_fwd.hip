@@ -16,10 +16,37 @@ namespace hode {
 // PACE: every wave sets its issue priority from the share of its own work that is left (pace_prio, hode_solve_body.h), so that the two
 // waves of a SIMD reach the end of the launch together.  The product library always paces; the lab library and experiment builds can
 // switch it off for A/B runs (fwd_pace() below, -DHODE_FWD_NOPACE).
+// ROT: how many of a hidden layer's 15 rotations a kernel fetches through LDS instead of DPP (mlp_hidden_blk_lds, hode_device.h: K, and
+// LEAN = its form that lands two of them in v9 / v11); 0 = mlp_hidden_blk.  A compile-time choice per instantiation, by the registers
+// it has (hipcc -Rpass-analysis=kernel-resource-usage; no instantiation may gain scratch or lose occupancy over K = 0):
+//   three hidden matrices (NL = 4): 256 registers, none to spare.  The lean K = 8 costs 8 and fits where K = 0 left that many: DP5(4)
+//     without tape, Hill term or the MULTI loop (the benchmark kernel), and RK4 unless it tapes AND carries the Hill term; the others
+//     keep K = 0 (the taping DP5(4) goes 0 -> 16 B of scratch with K = 4 already)
+//   two (NL = 3): <= 217 registers at K = 12, every instantiation takes it
+//   one (NL = 2): three to four waves per SIMD, a regime the microbenchmark did not cover, and RK4 + tape + Hill term would drop from four
+//     waves to three: K = 0
+// Experiment builds (tools/build_variant.sh) force one form on every fp32 instantiation with a hidden matrix:
+// -DHODE_FWD_LDS_ROT=<0|4|8|12> [-DHODE_FWD_LDS_ROT_LEAN=1, with 8].
+template <typename R, int NL, int METHOD, bool TAPE, bool GD, bool MULTI> struct FwdRot {
+#ifdef HODE_FWD_LDS_ROT
+    static constexpr int K = (sizeof(R) == 4 && NL >= 2) ? HODE_FWD_LDS_ROT : 0;
+#ifdef HODE_FWD_LDS_ROT_LEAN
+    static constexpr bool LEAN = K > 0 && HODE_FWD_LDS_ROT_LEAN;
+#else
+    static constexpr bool LEAN = false;
+#endif
+#else
+    static constexpr bool kRoom4 = METHOD == HODE_METHOD_DP54 ? (!TAPE && !GD && !MULTI) : !(TAPE && GD);
+    static constexpr int K = sizeof(R) != 4 ? 0 : NL == 3 ? 12 : (NL == 4 && kRoom4) ? 8 : 0;
+    static constexpr bool LEAN = K == 8;
+#endif
+};
+
 template <typename R, int NL, int METHOD, int LB, bool TAPE, bool GD, bool MULTI, bool PACE>
 __global__ __launch_bounds__(64, LB) void solve_fwd_kernel(const SolveArgs<R> a, const int chunk)
 {
     HODE_WL(0);
+    using Rot = FwdRot<R, NL, METHOD, TAPE, GD, MULTI>;
     __shared__ R rows[8 * kWave];             // tableau coefficient rows (hode_device.h)
     __shared__ R cvec[8];                     // tableau nodes c[s] as reals
     __shared__ R ybuf[kWave + 8];             // output staging: rows of 6 reals are gathered into 256-byte stores
@@ -29,13 +56,17 @@ __global__ __launch_bounds__(64, LB) void solve_fwd_kernel(const SolveArgs<R> a,
 
     tableau_rows_store<R>(rows, METHOD, lane, 64);
     if (lane < 8) cvec[lane] = (R)kTableau[METHOD].c[lane];
-    MlpRegs<R, NL> W;
+    std::conditional_t<(Rot::K > 0), MlpRegsRot<NL, Rot::K, Rot::LEAN>, MlpRegs<R, NL>> W;
+    if constexpr (Rot::K > 0) {
+        __shared__ float rotbuf[kRotBufElems];    // the hidden layers' rotation operands (this wave's: one wave per workgroup)
+        W.rot = rot_lane_addr((unsigned)(size_t)(__attribute__((address_space(3))) float *)rotbuf, lane);
+    }
     mlp_load<R, NL>(W, a.nn_p + (size_t)set * a.nn_stride, a.H, lane);
     OdeP<R> o;
     ode_load(o, a.ode_p + 17 * set);
     __syncthreads();
     HODE_WL(1);
-    const RhsRegs<R, NL, MlpRegs<R, NL>> rhs{W, o, lane};
+    const RhsRegs<R, NL, decltype(W)> rhs{W, o, lane};
     if constexpr (MULTI) {
         const int b1 = (b0 + chunk < a.B) ? b0 + chunk : a.B;
         const int per = a.T - 1;              // grid intervals of one trajectory; the pace is taken over the whole chunk

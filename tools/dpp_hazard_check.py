@@ -13,7 +13,9 @@ reports each DPP / swap read whose source register was written by a VALU instruc
 Second check (the adjoint reads LDS through inline asm, with its own counted `s_waitcnt lgkmcnt(n)`, because hipcc would otherwise wait
 for every outstanding vector-memory operation in front of a read that may alias an LDS-DMA target): no instruction may name the
 destination registers of an LDS read before a wait has covered it -- hipcc does not know that the asm's outputs are not there yet and is
-free to copy them.  LDS operations return in order: `lgkmcnt(n)` leaves the last n of them pending."""
+free to copy them.  LDS operations return in order: `lgkmcnt(n)` leaves the last n of them pending.  A packed fp32 instruction
+names only the halves of its 64-bit sources that op_sel / op_sel_hi select: the hybrid hidden layer of the forward kernels
+(mlp_hidden_blk_lds, lean form) fetches into v9 and v11 while its DPP part still reads the LOW halves of v[8:9] and v[10:11]."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hybrid-ode-for-glp-1-and-glucose_amd", "csrc")
@@ -31,6 +33,32 @@ def regs(tok):
     if m:
         return set(range(int(m.group(1)), int(m.group(2)) + 1))
     return set()
+
+
+def named_regs(op, ops, line):
+    """registers an instruction names; for v_pk_*_f32 / v_pk_mov_b32 (64-bit operands) only the selected halves of the sources --
+    and every register of the instruction whenever a source is not a plain register or pair, so that this can only miss less"""
+    if not (op.startswith("v_pk_") and op.endswith(("_f32", "_b32"))):
+        return set().union(*(regs(o) for o in ops)) if ops else set()
+    sel = {"op_sel": [0, 0, 0], "op_sel_hi": [1, 1, 1]}
+    for key in sel:
+        m = re.search(key + r":\[([01,]+)\]", line)
+        if m:
+            v = [int(x) for x in m.group(1).split(",")]
+            sel[key][:len(v)] = v
+    everything = set().union(*(regs(o) for o in ops)) if ops else set()
+    end = next((i for i, o in enumerate(ops) if ":" in o and not o.startswith(("v[", "s["))), len(ops))
+    srcs = ops[1:end]                                   # what stands between the destination and the first modifier
+    if not 2 <= len(srcs) <= 3 or not all(re.fullmatch(r"v\[\d+:\d+\]|v\d+|s\[\d+:\d+\]|s\d+", o) for o in srcs):
+        return everything                               # a source form this does not know (|v|, neg, a literal): name all of them
+    out = regs(ops[0]) if ops else set()
+    for i, o in enumerate(srcs):
+        r = sorted(regs(o))
+        if len(r) == 2:
+            out |= {r[h] for h in {sel["op_sel"][i], sel["op_sel_hi"][i]}}
+        else:
+            out |= set(r)
+    return out
 
 
 total = 0
@@ -63,7 +91,7 @@ for src in srcs:
             elif "vmcnt" not in line and "expcnt" not in line:          # a numeric s_waitcnt: assume it waits for everything
                 lds_q = []
         elif kernel and lds_q:
-            named = set().union(*(regs(o) for o in ops)) if ops else set()
+            named = named_regs(op, ops, line)
             for dst in lds_q:
                 if dst & named:
                     total += 1
