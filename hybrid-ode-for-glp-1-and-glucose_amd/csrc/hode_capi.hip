@@ -4,7 +4,6 @@
 #include "hode_kernels.h"
 #include <math.h>
 #include <string.h>
-#include "hode_device.h"
 
 using namespace hode;
 

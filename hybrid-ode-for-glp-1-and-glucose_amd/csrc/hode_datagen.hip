@@ -22,11 +22,7 @@ __constant__ double kDPE[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 172
 // x^p for the Hill / power-law terms.  exp(p*log x) costs ~1/3 of ocml's correctly rounded pow (which carries log x
 // in double-double); its error is |p ln x| ulp <~ 10 ulp = 1e-15 here, far below the integration tolerance.
 // Same special values as numpy's float power on this path: 0^p = 0 (p > 0), x < 0 -> NaN, x^0 = 1.
-#ifdef HODE_4GI_EXACT_POW
-__device__ __forceinline__ double powr_(double x, double p) { return pow(x, p); }
-#else
 __device__ __forceinline__ double powr_(double x, double p) { return p == 0.0 ? 1.0 : exp(p * log(x)); }
-#endif
 
 // per-subject constants of generate4GI.py:94-116 (they depend on the subject's baselines only)
 struct Subject {

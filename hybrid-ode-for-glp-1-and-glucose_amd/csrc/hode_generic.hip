@@ -19,6 +19,7 @@
 // DESIGN.md section 4.6 has the measurements that led here.  The integrator, controller, tape format and state layout are those
 // of the tuned path (hode_solve_body.h); CPU restatement: oracle/hode_oracle_impl.h (HODE_MAXH 128, HODE_MAXL 8).
 #include "hode_solve_body.h"
+#include "hode_adjoint.h"
 #include <type_traits>
 
 // HODE_GENERIC_GIN: this file compiled a second time by hode_generic_gin.hip.  The #ifdef HODE_GENERIC_GIN blocks below add the input
@@ -578,7 +579,7 @@ __device__ __forceinline__ R rhs_vjp_stream(const StreamNet<R> &n, const EW &ew,
                                             bool use_gd, int lane, const R *__restrict__ rec, R kb, R &go, R *gt_out, int part,
                                             R *__restrict__ xch, ACC &acc, int &xpar
 #ifdef HODE_GENERIC_GIN
-                                            , R *gin_out             // the input cotangents of this evaluation (input_vjp, hode_device.h)
+                                            , R *gin_out             // the input cotangents of this evaluation (input_vjp, hode_adjoint.h)
 #endif
                                             )
 {

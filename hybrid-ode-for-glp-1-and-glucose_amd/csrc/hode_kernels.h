@@ -96,6 +96,8 @@ inline int layers_of(int L) { return L & 0xff; }
 inline int act_of(int L) { return (L >> 8) & 0xff; }
 // (ReLU only: every other activation takes the generic kernels whatever the shape)
 inline bool tuned_shape(int H, int L) { return act_of(L) == HODE_ACT_RELU && H <= 64 && layers_of(L) <= 4; }
+// reals of one network's flat parameter vector: W1[H][9], b1 | (L - 1) x (W[H][H], b) | Wout[6][H], bout
+__host__ __device__ inline int nn_param_count(int H, int L) { L &= 0xff; return 9 * H + H + (L - 1) * (H * H + H) + 6 * H + 6; }   // (L may carry an activation code in bits 8..15)
 int launch_adam(hipStream_t s, int64_t n, float *p, const float *g, float *m, float *v, float lr, float b1,
                 float b2, float eps, int step, float max_norm, float grad_scale, float wd, void *scratch);
 int launch_mse(hipStream_t s, int64_t n, const float *y, const float *obs, float scale, double *loss, float *gy);
@@ -299,8 +301,7 @@ inline size_t tape_total_bytes(int B, int max_steps, size_t elem, int H, int L)
     // (generic shapes: the fp32 team kernels write gradient rows as well since round 4; fp64 and networks with more than four hidden
     //  matrices keep the coalesced atomics of hode_generic.hip)
     if (!tuned_shape(H, L) && elem != 4) return o;
-    const int P = 9 * H + H + (layers_of(L) - 1) * (H * H + H) + 6 * H + 6;
-    return o + (size_t)adj_partial_rows(B) * adj_partial_rowlen(P) * elem;
+    return o + (size_t)adj_partial_rows(B) * adj_partial_rowlen(nn_param_count(H, L)) * elem;
 }
 #ifdef HODE_LAB
 int launch_solve_bwd_split(hipStream_t s, const AdjArgs<float> &a, int L, int method);   // lab/hode_solve_bwd_split.hip (fp32, tuned shapes)

@@ -7,7 +7,7 @@
 // The MSE pass replaces F.mse_loss(predictions, observations) and its autograd
 // (models/hybrid_ode_nn.py:294): one read of y and obs, one write of dLoss/dy; HBM-bound,
 // 16-byte vectorised, grid-stride.
-#include "hode_device.h"
+#include "hode_xlane.h"
 #include "hode_kernels.h"
 
 namespace hode {

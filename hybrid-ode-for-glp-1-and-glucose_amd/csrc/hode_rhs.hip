@@ -4,7 +4,7 @@
 // ODECore.forward (models/ode_core.py:81-166) + NNResidual.forward (models/nn_residual.py:100-151)
 // for a batch of independent samples.  Same mapping as the solver: one sample per wavefront, one
 // hidden unit per lane; a workgroup of 4 waves loads the weights once and loops over samples.
-#include "hode_device.h"
+#include "hode_rhs_eval.h"
 #include "hode_kernels.h"
 
 namespace hode {

@@ -1,5 +1,5 @@
 // hode_solve_body.h -- the integration of ONE trajectory by ONE wavefront, shared by the two forward kernels
-// (register-resident weights: hode_solve_fwd.hip; hidden matrices in a workgroup-shared LDS image: hode_solve_fwd_wg.hip).
+// (register-resident weights: hode_solve_fwd.hip; hidden matrices in a workgroup-shared LDS image: lab/hode_solve_fwd_wg.hip).
 //
 // Replaces the body of the per-patient loop of HybridODENN.forward (reference models/hybrid_ode_nn.py:184-256): the
 // scipy.integrate.solve_ivp call, the RHS round trip through NumPy and the input interpolation (:210-231).
@@ -7,7 +7,8 @@
 // boundary (the meal forcing is piecewise linear with kinks there); FSAL derivative and step-size
 // proposal are carried across grid points.  CPU restatement: oracle/hode_oracle_impl.h (hode_oracle_solve).
 #pragma once
-#include "hode_device.h"
+#include "hode_tableau.h"
+#include "hode_rhs_eval.h"
 #include "hode_kernels.h"
 
 namespace hode {
@@ -44,7 +45,7 @@ template <> struct Eps<double> { static constexpr double v = 2.220446049250313e-
 
 // The right-hand side as a functor: F = rhs(t, Y, meal, tvns, gde, rec) evaluates f(t, x, u) in the replicated state
 // layout and, when rec != nullptr, records what the adjoint needs for this stage (layer activations + stage state) at rec.
-//   RhsRegs  : the tuned path -- every weight in registers (MlpRegs) or hidden matrices in an LDS image (MlpLds)
+//   RhsRegs  : the tuned path -- every weight in registers (MlpRegs) or, in the lab library, hidden matrices in an LDS image (MlpLds)
 //   RhsStream: the generic path (hode_generic.h) -- H <= 128, any depth, weights streamed from L2
 template <typename R, int NL, typename WT> struct RhsRegs {
     const WT &W;
@@ -64,11 +65,7 @@ template <typename R, int NL, typename WT> struct RhsRegs {
             // store to the 8 reals -- identical bits per address -- instead of masking 56 lanes off (exec save / branch / restore)
             int l7 = lane & 7;
             asm volatile("" : "+v"(l7));                    // (recomputed per stage: a hoisted copy costs a VGPR the kernel does not have)
-#ifdef HODE_TAPE_NT
-            __builtin_nontemporal_store(Ys, rec + NL * kWave + l7);
-#else
             rec[NL * kWave + l7] = Ys;
-#endif
             return F;
         }
         return rhs_eval<R, NL, false>(W, o, ts, Ys, meal, tvns, gde, lane, (MlpActs<R, NL> *)nullptr);
@@ -92,7 +89,7 @@ template <typename R> __device__ __forceinline__ float rms6(float sum)
     else return sqrtf(sum / 6.0f);
 }
 
-// Dormand-Prince 5(4) as compile-time constants (the values of kTableau[HODE_METHOD_DP54], hode_device.h): the fp32 solve unrolls its
+// Dormand-Prince 5(4) as compile-time constants (the values of kTableau[HODE_METHOD_DP54], hode_tableau.h): the fp32 solve unrolls its
 // six stages with one register per stage derivative, so a stage combination is a chain of FMAs with literal coefficients
 namespace dp54c {
 constexpr double A[7][6] = {{0, 0, 0, 0, 0, 0},
@@ -143,20 +140,10 @@ __device__ __forceinline__ void pace_prio(int left, int total)
 {
     left = __builtin_amdgcn_readfirstlane(left);
     total = __builtin_amdgcn_readfirstlane(total);
-#if defined(HODE_FWD_PACE_LEVELS) && HODE_FWD_PACE_LEVELS == 4          // experiment builds (tools/build_variant.sh): linear quarters
-    if (4 * left > 3 * total) __builtin_amdgcn_s_setprio(3);
-    else if (2 * left > total) __builtin_amdgcn_s_setprio(2);
-    else if (4 * left > total) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-#elif defined(HODE_FWD_PACE_LEVELS) && HODE_FWD_PACE_LEVELS == 2        // two levels
-    if (2 * left > total) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-#else
     if (2 * left > total) __builtin_amdgcn_s_setprio(3);
     else if (8 * left > total) __builtin_amdgcn_s_setprio(2);
     else if (32 * left > total) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // rows  [8][64] tableau coefficient rows, cvec [8] tableau nodes (LDS, shared by the workgroup)

@@ -7,7 +7,7 @@
 // of each step.  Step sizes are treated as constants.
 // CPU restatement: oracle/hode_oracle_impl.h (hode_oracle_solve_bwd).
 //
-// Mapping: one trajectory per wavefront, one hidden unit per lane (see hode_device.h).
+// Mapping: one trajectory per wavefront, one hidden unit per lane (see hode_xlane.h).
 //   * the forward recorded, for every stage of every accepted step, the layer activations and the (compact)
 //     stage state on the "stage tape" in HBM (6.3 KB per step in fp32): the adjoint streams them back
 //     by LDS-DMA (global_load ... lds, one stage ahead, double buffered) instead of recomputing the
@@ -20,7 +20,8 @@
 //     outer-product FMAs sit between the issue and the use of every group of reads;
 //   * a wave loops over several trajectories and keeps accumulating; at the end the 8 waves of a
 //     workgroup reduce through LDS and flush coalesced atomics (12 k per workgroup).
-#include "hode_device.h"
+#include "hode_tableau.h"
+#include "hode_adjoint.h"
 #include "hode_kernels.h"
 #include <type_traits>
 #include <cstdlib>
@@ -34,18 +35,14 @@ template <typename R> __device__ __forceinline__ R inp_at_b(const R *__restrict_
 }
 
 // LDS layout of the adjoint workgroup (kBwdWaves waves sharing one parameter set):
-//   wt    [(NL-1)][64*64]   transposed hidden matrices, rotating-operand order (hode_device.h: wt_rot_store)
+//   wt    [(NL-1)][64*64]   transposed hidden matrices, rotating-operand order (hode_adjoint.h: wt_rot_store)
 //   rowsT [8][64]           transposed tableau rows A[lane>>3][s]; row 7 = 1 for the solution stages
 constexpr int kBwdWaves = 8;
-// stage records in flight AHEAD of the one being processed (LDS-DMA ring of kBwdAhead<R> + 1 slots per wave).  One record
-// ahead is ~2 900 cycles of lead; two (-DHODE_BWD_AHEAD=2, counted vmcnt wait) were measured at the same 8.1 ms: the
-// record DMA is not what the stage loop waits for
-#ifndef HODE_BWD_AHEAD
-#define HODE_BWD_AHEAD 1
-#endif
-// fp64 (parity builds): the 96 KB transposed-matrix image leaves room for one record ahead only
-template <typename R> constexpr int kBwdAhead = (sizeof(R) == 4) ? HODE_BWD_AHEAD : 1;
-template <typename R> constexpr int kBwdRing = kBwdAhead<R> + 1;
+// stage records in flight AHEAD of the one being processed (LDS-DMA ring of kBwdAhead + 1 slots per wave).  One record
+// ahead is ~2 900 cycles of lead; two (a counted vmcnt wait) were measured at the same 8.1 ms: the record DMA is not what the
+// stage loop waits for -- and the fp64 builds' 96 KB transposed-matrix image leaves room for one record ahead only
+constexpr int kBwdAhead = 1;
+constexpr int kBwdRing = kBwdAhead + 1;
 //   edgeW [16+NL][64]       first/last layer weights (fp32 build; shared)
 //   edgeG [waves][16+NL][64] first/last layer gradient accumulators (fp32 build; per wave)
 //   rec   [waves][ring][NL+1][64] stage records (h_1..h_NL, state) arriving by LDS-DMA (global_load ... lds)
@@ -54,7 +51,7 @@ template <typename R, int NL> __host__ __device__ constexpr size_t bwd_lds_elems
 {
     return (size_t)(NL > 1 ? NL - 1 : 1) * kMaxH * kMaxH + 8 * kWave +
            (kEdgeLds<R> ? (size_t)(1 + kBwdWaves) * EdgeSlots<NL>::count * kWave : 0) +
-           (size_t)kBwdWaves * kBwdRing<R> * (NL + 1) * kWave;      // rec: [waves][ring][NL rows + state][64] stage-record ring
+           (size_t)kBwdWaves * kBwdRing * (NL + 1) * kWave;      // rec: [waves][ring][NL rows + state][64] stage-record ring
 }
 
 // The adjoint reads, for every stage of every accepted step, what the forward recorded on the stage
@@ -86,7 +83,7 @@ __global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !W
     constexpr int kRows = NL;                         // rows of 64 in a stage record (h_1 .. h_NL) ...
     constexpr int kSlot = kRows * kWave + 8;          // ... followed by the stage state in 8 reals
     constexpr int kBuf = kRows * kWave + kWave;       // one slot of a wave's record ring: the rows + the state (8 of 64 used)
-    constexpr int kRing = kBwdRing<R>;
+    constexpr int kRing = kBwdRing;
 
     const R *__restrict__ nn_set = a.nn_p + (size_t)set * a.P;
     using ES = EdgeSlots<NL>;
@@ -188,10 +185,7 @@ __global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !W
         // half of the wave's double buffer, the record of the next stage (also across step boundaries) lands
         // in the other half.
         // records are consumed in the order (n-1, S-1), (n-1, S-2), ..., (0, 0); (pst, ps) walks kBwdAhead records ahead
-        constexpr int kAhead = kBwdAhead<R>;
-        constexpr int kDmaOps = kRows * (int)(sizeof(R) / 4) + 1;                 // DMA instructions per record
-        constexpr int kWaitYounger = 0x0f70 | ((kDmaOps * (kAhead - 1)) & 15) | (((kDmaOps * (kAhead - 1)) >> 4) << 14);
-        static_assert(kDmaOps * (kAhead - 1) < 64, "vmcnt field");
+        constexpr int kAhead = kBwdAhead;
         int cur = 0, pst = n - 1, ps = S - 1, ahead = 0;                         // ahead = records issued and not yet consumed
         auto issue_next = [&]() {
             if (pst < 0) return;
@@ -240,9 +234,8 @@ __global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !W
 #pragma unroll 1
             for (int s = S - 1; s >= 0; --s) {
                 // record (st, s) was DMA'd into ring slot `cur` kBwdAhead stages ago.  The only outstanding VMEM ops are our
-                // DMAs and they complete in issue order: wait until at most the YOUNGER records are still in flight
-                if (ahead == kAhead && kAhead > 1) __builtin_amdgcn_s_waitcnt(kWaitYounger);
-                else __builtin_amdgcn_s_waitcnt(0x0f70);       // vmcnt(0): tail of the trajectory
+                // DMAs: with one record ahead, all of them belong to this record
+                __builtin_amdgcn_s_waitcnt(0x0f70);            // vmcnt(0)
                 __builtin_amdgcn_wave_barrier();
                 --ahead;                                       // slot `cur` is being consumed; the slot behind the ring frees up
                 {

@@ -39,17 +39,12 @@
 // Determinism: every A-wave adds its slots' products in slot order, the waves of a matrix are summed in rank order, the workgroup
 // writes ONE gradient row to a.partials and adj_reduce_kernel adds the rows in workgroup order: no floating-point atomics
 // anywhere, the same inputs give the same bits.
-#include "hode_device.h"
+#include "hode_tableau.h"
+#include "hode_adjoint.h"
 #include "hode_kernels.h"
 #include <cstdlib>
 
 namespace hode {
-
-// 1: the propagation waves read the lane's 16-lane row of delta back from the hand-off slot (four 16-byte broadcast reads) and take
-//    the operands of the packed FMAs from there (ws_wt_group_lb); 0: round 3's form, one v_mov_b32_dpp row_ror:n per rotation
-#ifndef HODE_WS_PROP_LB
-#define HODE_WS_PROP_LB 1
-#endif
 
 namespace {
 
@@ -79,7 +74,7 @@ template <int NL, int U> constexpr size_t ws_lds_elems()
            (size_t)kWsP * U * 2 * ws_hand_elems<NL>() + 2 * 16 + 16 + (size_t)kWsP * U * 2 * kWave + 32 + 6 * kWave;
 }
 
-// J_mech^T kb as mech_vjp (hode_device.h) computes it, with the five terms evaluated on ALL lanes and selected by lane -- the
+// J_mech^T kb as mech_vjp (hode_adjoint.h) computes it, with the five terms evaluated on ALL lanes and selected by lane -- the
 // propagation waves have the registers for it, and the exec-masked regions hipcc builds out of a nested ?: cost a
 // v_cmp / s_and_saveexec / s_cbranch_execz round trip per term on a wave whose time is its instruction count
 template <bool GODE>
@@ -105,15 +100,17 @@ __device__ __forceinline__ float ws_mech_vjp(const OdeP<float> &o, float G, floa
     return r;
 }
 
-// delta_prev = W^T delta in the ROW-BLOCK order of the forward's hidden layer (hode_device.h mlp_hidden_blk), the transposed matrix
-// in an LDS image of its own (wt_blk_store below):
-//     img[l][n][lane (r, i)] = { W_l[16 r + ((i - n) & 15)][16 w + i] : w = 0..3 }            n = 0..15
-// so delta_{l+1} in its NATURAL layout (unit per lane) is the DPP operand as it is -- no row replication (rows_replicate: 9
-// instructions per matrix and trajectory) --, the 16-byte word of rotation n holds the two weight PAIRS of the four accumulators, and
-// a rotation is one v_mov_b32_dpp + two v_pk_fma_f32 (both halves take the low half of the moved operand).  The four accumulators
-// are added over the rows and transposed by the forward's 2 + 1 swaps and 3 adds.  55 vector instructions per matrix and trajectory
-// instead of 76 (rotating-operand order of wt_rot_store: 64 v_fmac_f32_dpp, one per weight); the reads are issued two groups of four
-// rotations ahead of their use as before: the propagation wave has no outer-product FMAs to put between a read and its first use.
+// delta_prev = W^T delta in the ROW-BLOCK order of the forward's hidden layer (hode_mlp.h mlp_hidden_blk), the transposed matrix
+// in an LDS image of its own (wt_blk_store below), columns in their natural order:
+//     img[l][n][lane (r, i)] = { W_l[16 r + n][16 w + i] : w = 0..3 }            n = 0..15
+// The 16-byte word of column n holds the two weight PAIRS of the four accumulators; the wave reads the lane's 16-lane row of delta_{l+1}
+// back from the hand-off slot it has just written (four 16-byte broadcast reads) and the packed FMAs take their operand from there
+// (ws_wt_group_lb) -- no row replication (rows_replicate: 9 instructions per matrix and trajectory) and no cross-lane move.  The four
+// accumulators are added over the rows and transposed by the forward's 2 + 1 swaps and 3 adds.  Round 3's form -- the rotated image
+// W_l[16 r + ((i - n) & 15)][16 w + i] and one v_mov_b32_dpp row_ror:n per rotation, 55 vector instructions per matrix and trajectory
+// instead of the 76 of wt_rot_store's order -- measured 5.70 against 5.66 ms (profiles/r04_adj_prop_lb_ab.log).
+// The reads are issued two groups of four columns ahead of their use: the propagation wave has no outer-product FMAs to put between
+// a read and its first use.
 __device__ __forceinline__ void wt_blk_store(float *__restrict__ wt, const float *__restrict__ nn_p, int H, int NLm1, int tid, int nthreads)
 {
     const float *Wl = nn_p + 9 * H + H;
@@ -121,51 +118,18 @@ __device__ __forceinline__ void wt_blk_store(float *__restrict__ wt, const float
         for (int e = tid; e < kMaxH * kMaxH; e += nthreads) {
             const int w = ((e & 1) << 1) | ((e >> 1) & 1), lane = (e >> 2) & 63, n = e >> 8;      // word = { w0, w2, w1, w3 }: the pairs (a0, a2), (a1, a3)
             const int i = lane & 15, r = lane >> 4;
-#if HODE_WS_PROP_LB
             const int row = 16 * r + n, col = 16 * w + i;                                          // natural column order (ws_wt_group_lb)
-#else
-            const int row = 16 * r + ((i - n) & 15), col = 16 * w + i;
-#endif
             wt[(size_t)l * kMaxH * kMaxH + e] = (row < H && col < H) ? Wl[(size_t)row * H + col] : 0.f;
         }
         Wl += (size_t)H * H + H;
     }
 }
 
-// rotations 4 G .. 4 G + 3 (the words w[0..3]) of one matrix for one trajectory: d = delta in the natural layout
-template <int G> __device__ __forceinline__ void ws_wt_group(const Vec4<float> (&w)[4], const float d, f2_t &a01, f2_t &a23)
-{
-    static_assert(G >= 0 && G < 4, "four groups of four rotations");
-#define HODE_WS_STEP(I, N)                                                                                                      \
-    {                                                                                                                           \
-        float lo;                                                                                                               \
-        asm("v_mov_b32_dpp %0, %1 row_ror:" #N " row_mask:0xf bank_mask:0xf" : "=v"(lo) : "v"(d));                              \
-        f2_t hr;                                                                                                                \
-        hr.x = lo;                                                                                                              \
-        const f2_t w01 = {w[I].v[0], w[I].v[1]}, w23 = {w[I].v[2], w[I].v[3]};                                                  \
-        asm("v_pk_fma_f32 %0, %2, %4, %0 op_sel_hi:[1,0,1]\n\tv_pk_fma_f32 %1, %3, %4, %1 op_sel_hi:[1,0,1]"                   \
-            : "+v"(a01), "+v"(a23) : "v"(w01), "v"(w23), "v"(hr));                                                              \
-    }
-    if constexpr (G == 0) {
-        // rotation 0 is the lane's own delta; products start the sums (and are the wait states the first DPP read of d needs)
-        const f2_t w01 = {w[0].v[0], w[0].v[1]}, w23 = {w[0].v[2], w[0].v[3]};
-        f2_t hh;
-        hh.x = d;
-        asm("v_pk_mul_f32 %0, %2, %4 op_sel_hi:[1,0]\n\tv_pk_mul_f32 %1, %3, %4 op_sel_hi:[1,0]" : "=&v"(a01), "=&v"(a23) : "v"(w01), "v"(w23), "v"(hh));
-        HODE_WS_STEP(1, 1) HODE_WS_STEP(2, 2) HODE_WS_STEP(3, 3)
-    } else if constexpr (G == 1) {
-        HODE_WS_STEP(0, 4) HODE_WS_STEP(1, 5) HODE_WS_STEP(2, 6) HODE_WS_STEP(3, 7)
-    } else if constexpr (G == 2) {
-        HODE_WS_STEP(0, 8) HODE_WS_STEP(1, 9) HODE_WS_STEP(2, 10) HODE_WS_STEP(3, 11)
-    } else {
-        HODE_WS_STEP(0, 12) HODE_WS_STEP(1, 13) HODE_WS_STEP(2, 14) HODE_WS_STEP(3, 15)
-    }
-#undef HODE_WS_STEP
-}
 // Columns 4 G .. 4 G + 3 (the words w[0..3]: {W_l[16 r + c][16 w + i] : w}, natural column order) of one matrix for one trajectory;
 // q = delta[16 r + 4 G .. + 3], the quarter of the lane's row that the wave read back from the hand-off slot: the packed FMAs pick
 // the low / high half of a loaded register pair (op_sel) -- no cross-lane instruction.  15 v_mov_b32_dpp fewer per matrix and
-// trajectory than ws_wt_group; same products per accumulator in column order instead of rotation order.
+// trajectory than round 3's form (one v_mov_b32_dpp row_ror:n per rotation); same products per accumulator in column order instead of
+// rotation order.
 typedef float ws_f4_t __attribute__((ext_vector_type(4)));
 template <int G> __device__ __forceinline__ void ws_wt_group_lb(const Vec4<float> (&w)[4], const ws_f4_t q, f2_t &a01, f2_t &a23)
 {
@@ -261,11 +225,9 @@ __device__ __forceinline__ void ws_wt_mul_lb(const float *__restrict__ wt, const
 #pragma unroll
     for (int i = 0; i < 4; ++i) w1[i] = nx4[(4 + i) * kMaxH + lane];
 #pragma unroll
-    for (int u = 0; u < U; ++u) out[u] = blk_rows_finish<false, false>(a01[u], a23[u], 0.f);
+    for (int u = 0; u < U; ++u) out[u] = blk_rows_finish(a01[u], a23[u]);      // hode_mlp.h: pairs (a0, a2), (a1, a3)
 }
 
-// the four accumulators -> (W^T delta)[unit of the lane]: hode_device.h blk_rows_finish (pairs (a0, a2), (a1, a3); no bias)
-__device__ __forceinline__ float ws_wt_finish(const f2_t a02, const f2_t a13) { return blk_rows_finish<false, false>(a02, a13, 0.f); }
 // The sixteen 16-byte reads of a matrix are issued ahead of their use: on entry w0 / w1 hold the words of groups 0 and 1 (loaded
 // while the PREVIOUS matrix -- or, for the first matrix of a stage, the previous iteration's tail -- was being worked on), groups
 // 2 and 3 follow into the buffer the group before them has freed, and on exit w0 / w1 hold groups 0 and 1 of `wt_next`: the
@@ -277,41 +239,6 @@ __device__ __forceinline__ void ws_wt_preload(const float *__restrict__ wt, int 
     for (int i = 0; i < 4; ++i) w0[i] = wt4[(0 + i) * kMaxH + lane];
 #pragma unroll
     for (int i = 0; i < 4; ++i) w1[i] = wt4[(4 + i) * kMaxH + lane];
-}
-// U trajectories: the same sixteen 16-byte reads feed all of them (half the LDS traffic per trajectory at U = 2), and their
-// accumulator sets are independent instruction chains
-template <int U>
-__device__ __forceinline__ void ws_wt_mul(const float *__restrict__ wt, const float *__restrict__ wt_next, int lane, const float (&d)[U],
-                                          float (&out)[U], Vec4<float> (&w0)[4], Vec4<float> (&w1)[4])
-{
-    const Vec4<float> *wt4 = reinterpret_cast<const Vec4<float> *>(wt), *nx4 = reinterpret_cast<const Vec4<float> *>(wt_next);
-    f2_t a01[U], a23[U];                            // started by group 0
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < U; ++u) ws_wt_group<0>(w0, d[u], a01[u], a23[u]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w0[i] = wt4[(8 + i) * kMaxH + lane];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < U; ++u) ws_wt_group<1>(w1, d[u], a01[u], a23[u]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w1[i] = wt4[(12 + i) * kMaxH + lane];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < U; ++u) ws_wt_group<2>(w0, d[u], a01[u], a23[u]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w0[i] = nx4[(0 + i) * kMaxH + lane];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < U; ++u) ws_wt_group<3>(w1, d[u], a01[u], a23[u]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w1[i] = nx4[(4 + i) * kMaxH + lane];
-#pragma unroll
-    for (int u = 0; u < U; ++u) out[u] = ws_wt_finish(a01[u], a23[u]);
 }
 
 }  // namespace
@@ -535,7 +462,7 @@ __global__ __launch_bounds__(64 * kWsWaves) void solve_bwd_ws_kernel(const AdjAr
         bool active[U], ok[U];
         const R *__restrict__ stg[U];
         {
-            // first-layer weights of the six state inputs in the rotating order of out_rot (hode_device.h): lane (r, i) keeps, for
+            // first-layer weights of the six state inputs in the rotating order of out_rot (hode_mlp.h): lane (r, i) keeps, for
             // input o = i & 7, w1r[n] = W1[16 r + ((i - n) & 15)][1 + o] (GLP1, o = 3, feeds inputs 4 and 7; zero for o >= 6), so
             // that the state cotangent W1^T delta_1 is 8 FMAs on delta_1 in its natural layout + a 7-instruction reduction that
             // lands in the replicated layout of the state -- 15 instructions instead of six products + the 30 of
@@ -768,14 +695,10 @@ __global__ __launch_bounds__(64 * kWsWaves) void solve_bwd_ws_kernel(const AdjAr
                     for (int u = 0; u < U; ++u) dp[u] = d[u] * 0.5f;
                 } else {
                     // (the matrix after this one: l - 2, or -- behind the last -- the first matrix of the next stage)
-#if HODE_WS_PROP_LB
                     unsigned drow[U];
 #pragma unroll
                     for (int u = 0; u < U; ++u) drow[u] = (unsigned)(size_t)(__attribute__((address_space(3))) R *)(hd[u] + l * kWave + (lane & 48));
                     ws_wt_mul_lb<U>(wt + (size_t)(l - 1) * kMaxH * kMaxH, wt + (size_t)(l >= 2 ? l - 2 : NM - 1) * kMaxH * kMaxH, lane, drow, dp, wq0, wq1);
-#else
-                    ws_wt_mul<U>(wt + (size_t)(l - 1) * kMaxH * kMaxH, wt + (size_t)(l >= 2 ? l - 2 : NM - 1) * kMaxH * kMaxH, lane, d, dp, wq0, wq1);
-#endif
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {

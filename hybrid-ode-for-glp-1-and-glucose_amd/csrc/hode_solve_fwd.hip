@@ -16,7 +16,7 @@ namespace hode {
 // PACE: every wave sets its issue priority from the share of its own work that is left (pace_prio, hode_solve_body.h), so that the two
 // waves of a SIMD reach the end of the launch together.  The product library always paces; the lab library and experiment builds can
 // switch it off for A/B runs (fwd_pace() below, -DHODE_FWD_NOPACE).
-// ROT: how many of a hidden layer's 15 rotations a kernel fetches through LDS instead of DPP (mlp_hidden_blk_lds, hode_device.h: K, and
+// ROT: how many of a hidden layer's 15 rotations a kernel fetches through LDS instead of DPP (mlp_hidden_blk_lds, hode_mlp.h: K, and
 // LEAN = its form that lands two of them in v9 / v11); 0 = mlp_hidden_blk.  A compile-time choice per instantiation, by the registers
 // it has (hipcc -Rpass-analysis=kernel-resource-usage; no instantiation may gain scratch or lose occupancy over K = 0):
 //   three hidden matrices (NL = 4): 256 registers, none to spare.  The lean K = 8 costs 8 and fits where K = 0 left that many: DP5(4)
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(64, LB) void solve_fwd_kernel(const SolveArgs<R> a,
 {
     HODE_WL(0);
     using Rot = FwdRot<R, NL, METHOD, TAPE, GD, MULTI>;
-    __shared__ R rows[8 * kWave];             // tableau coefficient rows (hode_device.h)
+    __shared__ R rows[8 * kWave];             // tableau coefficient rows (hode_tableau.h)
     __shared__ R cvec[8];                     // tableau nodes c[s] as reals
     __shared__ R ybuf[kWave + 8];             // output staging: rows of 6 reals are gathered into 256-byte stores
     const int lane = threadIdx.x;
@@ -103,16 +103,6 @@ static void launch_one(hipStream_t s, const SolveArgs<R> &a)
             hipLaunchKernelGGL((solve_fwd_kernel<R, NL, METHOD, LB, TAPE, GD, true, PACE>), dim3((a.B + chunk - 1) / chunk), dim3(64), 0, s, a, chunk);
             return;
         }
-#ifdef HODE_FWD_ONE_ROUND
-        // experiment builds (-DHODE_FWD_ONE_ROUND=<longest chunk>): a batch of more than one round of the 2 048 wave slots as ONE round of
-        // waves with ceil(B / 2 048) trajectories each -- one weight prologue and one dispatch per slot
-        constexpr int kWaveSlots = 2048;      // 256 CUs x 4 SIMDs x 2 waves of this kernel
-        if (a.n_sets == 1 && a.B > kWaveSlots && (a.B + kWaveSlots - 1) / kWaveSlots <= HODE_FWD_ONE_ROUND) {
-            const int chunk = (a.B + kWaveSlots - 1) / kWaveSlots;
-            hipLaunchKernelGGL((solve_fwd_kernel<R, NL, METHOD, LB, TAPE, GD, true, PACE>), dim3((a.B + chunk - 1) / chunk), dim3(64), 0, s, a, chunk);
-            return;
-        }
-#endif
     }
     hipLaunchKernelGGL((solve_fwd_kernel<R, NL, METHOD, LB, TAPE, GD, false, PACE>), dim3(a.B), dim3(64), 0, s, a, 1);
 }
@@ -180,13 +170,13 @@ template int launch_solve_fwd<double>(hipStream_t, const SolveArgs<double> &, in
 }  // namespace hode
 
 #ifdef HODE_FWD_TRACE
-// experiment build only: the stamps of hode_device.h's g_ft (this translation unit's copy: the forward kernels are instantiated here)
+// experiment build only: the stamps of hode_rhs_eval.h's g_ft (this translation unit's copy: the forward kernels are instantiated here)
 extern "C" int hode_lab_fwd_trace(unsigned long long *dst, int n_words, unsigned *count)
 {
     if (hipMemcpyFromSymbol(count, HIP_SYMBOL(hode::g_ft_n), sizeof(unsigned)) != hipSuccess) return -1;
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(hode::g_ft), sizeof(unsigned long long) * (size_t)n_words) == hipSuccess ? 0 : -1;
 }
-// the wave-lifetime records of the last forward launch: n_waves <= kWlWaves records of 8 words (hode_device.h, g_wl)
+// the wave-lifetime records of the last forward launch: n_waves <= kWlWaves records of 8 words (hode_rhs_eval.h, g_wl)
 extern "C" int hode_lab_fwd_lifetimes(unsigned long long *dst, int n_waves)
 {
     if (n_waves < 0 || n_waves > hode::kWlWaves) return -1;

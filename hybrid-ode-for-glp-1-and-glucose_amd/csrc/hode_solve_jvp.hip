@@ -7,7 +7,7 @@
 // differentiates the same thing: the two are transposes of each other, so <gy, J v> = <J^T gy, v> to rounding.
 // CPU restatement of the adjoint it is the transpose of: oracle/hode_oracle_impl.h (hode_oracle_solve_bwd).
 //
-// Mapping: one trajectory per wavefront, one hidden unit per lane (hode_device.h), K_TILE directions per wave.
+// Mapping: one trajectory per wavefront, one hidden unit per lane (hode_xlane.h), K_TILE directions per wave.
 //   * the hidden matrices are loaded into VGPRs once per wave in the forward's register order (mlp_load), so a layer of the
 //     tangent, W_l d, is the forward's packed-FMA / DPP layer (mlp_hidden_blk) with a zero bias;
 //   * the ReLU derivative is the mask h_l > 0 of the taped activations (what the adjoint uses); nothing of the primal is
@@ -17,7 +17,8 @@
 //   * the mechanistic part J_x f . dY + J_theta f . v: the per-lane coefficients of the lane's component are computed once
 //     per stage (they depend on the stage state only) and every direction then costs 10 FMAs;
 //   * no atomics, no scratch in fp32, the tape is read-only.
-#include "hode_device.h"
+#include "hode_tableau.h"
+#include "hode_rhs_eval.h"
 #include "hode_kernels.h"
 
 namespace hode {
@@ -102,7 +103,7 @@ template <typename R, int NL, bool GD>
 __global__ __launch_bounds__(64 * kJvpWaves, 1) void solve_jvp_kernel(const JvpArgs<R> a, const int method)
 {
     constexpr int KT = kJvpTile<R>;
-    __shared__ R rows[8 * kWave];                 // tableau coefficient rows (hode_device.h: tableau_rows_store)
+    __shared__ R rows[8 * kWave];                 // tableau coefficient rows (hode_tableau.h: tableau_rows_store)
     const int lane = threadIdx.x & 63;
     const int c8 = lane & 7, grp = lane >> 3;
     const int wave = first_lane((int)(threadIdx.x >> 6));

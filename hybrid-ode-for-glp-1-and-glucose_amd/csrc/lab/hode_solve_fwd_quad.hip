@@ -9,7 +9,7 @@
 //
 // Here the four waves of a workgroup integrate four trajectories and SHARE the weights by columns: wave w keeps, of every
 // hidden matrix, the 16 columns 16w .. 16w+15 (48 registers for three matrices, in the rotating-operand order of
-// hode_device.h), and computes that quarter of the matrix-vector product for ALL FOUR trajectories -- the same 64
+// fmac_ror, hode_xlane.h), and computes that quarter of the matrix-vector product for ALL FOUR trajectories -- the same 64
 // v_fmac_f32_dpp per layer and wave as before.  Per layer the waves exchange through LDS
 //     1. their activation vectors (256 B each; wave w reads back, already replicated, the 16-lane row w of each of them),
 //     2. the partial sums for the three trajectories they do not own (3 x 256 B each),
@@ -34,6 +34,7 @@
 // not occupancy, LDS or the DPP rate of one of them but what they share -- ~550 instructions (363 VALU) per RHS and wave
 // through the same instruction front end.
 #include "../hode_solve_body.h"
+#include "hode_lab_layers.h"
 #include <cstdlib>
 
 namespace hode {

@@ -33,6 +33,7 @@
 // a zero activation until all four flags are down; all waves leave together.  The exchange area is double-buffered: a wave
 // can be at most one barrier ahead of its partners.
 #include "../hode_solve_body.h"
+#include "hode_lab_layers.h"
 #include <cstdlib>
 
 namespace hode {
@@ -82,7 +83,7 @@ template <int NL> struct MlpRows {
         any_active = false;
     }
 
-    // 64 FMAs of one layer as one asm statement (see mlp_hidden in hode_device.h for why)
+    // 64 FMAs of one layer as one asm statement (see mlp_hidden in hode_lab_layers.h for why)
     __device__ __forceinline__ void fma64(const float (&w)[16], float (&acc)[kRowsWaves]) const
     {
 #define HODE_RW(n)                                                                               \

@@ -1,5 +1,5 @@
 // hode_solve_fwd_wg.hip -- K2+K3, fp32 EXPERIMENT (HODE_FWD=wg): one trajectory per wavefront, WPB wavefronts per workgroup,
-// hidden weight matrices in ONE LDS image shared by the workgroup (hode_device.h: MlpLds).
+// hidden weight matrices in ONE LDS image shared by the workgroup (hode_lab_layers.h: MlpLds).
 //
 // Measured on MI355X, 4 096 x 241: 4.46-4.65 ms against 4.12 ms for the register kernel at every tuning point below
 // (all LDS / one matrix in registers / two; 8 or 16 waves per workgroup), bit-identical results.  The LDS pipe delivers
@@ -13,6 +13,7 @@
 // the 4 096-patient batch is exactly one workgroup per CU).  The arithmetic and its order are those of the register
 // kernel: both give the same bits (tests/test_hip_parity.py::test_fwd_workgroup_kernel_is_bitwise_the_register_kernel).
 #include "../hode_solve_body.h"
+#include "hode_lab_layers.h"
 #include <cstdlib>
 
 namespace hode {

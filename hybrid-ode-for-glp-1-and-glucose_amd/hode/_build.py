@@ -35,7 +35,8 @@ def source_stamp():
 
 
 def lab_source_stamp():
-    files = _stamp_inputs() + sorted(glob.glob(os.path.join(CSRC, "lab", "*.hip")))
+    """csrc/Makefile: STAMP_IN, then the lab library's own sorted lab/*.hip and sorted lab/*.h"""
+    files = _stamp_inputs() + sorted(glob.glob(os.path.join(CSRC, "lab", "*.hip"))) + sorted(glob.glob(os.path.join(CSRC, "lab", "*.h")))
     if not all(os.path.exists(f) for f in files):
         return None
     h = hashlib.sha256()

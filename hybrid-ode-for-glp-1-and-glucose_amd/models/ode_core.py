@@ -5,7 +5,7 @@ ode_core.py:34-79; equations: ode_core.py:104-161).  This module is the *definit
 17 physiological constants (buffers -> state_dict keys `ode_core.<name>`) and a plain-torch,
 autograd-differentiable evaluation used for Jacobians and unit tests.  The batched hot path
 (HybridODENN.ode_residual / forward) does not call this forward: it hands the 17 constants to
-the HIP kernels (csrc/hode_device.h: rhs_eval).
+the HIP kernels (csrc/hode_rhs_eval.h: rhs_eval).
 """
 from typing import Dict, Optional
 

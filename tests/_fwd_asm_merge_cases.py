@@ -1,5 +1,5 @@
 """The cases of tests/test_fwd_asm_merge_gpu.py, shared with tools/record_fwd_asm_merge.py (which records what the library
-of the commit BEFORE the change gives for them): the smallest shapes at which the fp32 register path of csrc/hode_device.h --
+of the commit BEFORE the change gives for them): the smallest shapes at which the fp32 register path of csrc/hode_mlp.h --
 mlp_hidden_blk, out_rot, the state broadcasts -- can go wrong.
 
 The networks are cut out of the golden 64 x 4 network (tests/golden/g0_weights_h64_l4.npz): the leading H units of the first

@@ -406,7 +406,7 @@ def test_cfg5_elbo_4x64_16_draws_value_and_gradient_vs_per_draw_oracle(monkeypat
     ode_err = {k: abs(float(gmu[k]) - float(gmu_o[k])) / (abs(float(gmu_o[k])) + 1e-12) for k in ode_keys}
     print("cfg5: d ELBO / d mu of the ODE constants, relative error", ode_err)
     # eight scalars of very different size, each a sum over 16 x 8 x 360 stages accumulated in ONE fp32 register per constant
-    # (hode_device.h mech_vjp).  As a vector in the posterior's own units (gradient x prior width: what an optimiser step on the
+    # (hode_adjoint.h mech_vjp).  As a vector in the posterior's own units (gradient x prior width: what an optimiser step on the
     # standardised parameter sees) 1e-3; each on its own 5e-2: rho's net gradient is what is left after d f / d rho =
     # lI GLP1 a_GI (G - G_b) has changed sign with G - G_b along every trajectory (measured 1.4e-2; a_GI 2.5e-4; the others 1e-5)
     sc = np.array([vp.prior_stds.get(k, 1.0) for k in ode_keys])

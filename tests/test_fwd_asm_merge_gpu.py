@@ -1,4 +1,4 @@
-"""mlp_hidden_blk (csrc/hode_device.h) issues each rotation's DPP move and its two packed FMAs from one asm statement, and the
+"""mlp_hidden_blk (csrc/hode_mlp.h) issues each rotation's DPP move and its two packed FMAs from one asm statement, and the
 pads of the layer finish and of out_rot that no hazard needs are gone.  Same instructions, same order per accumulator: the
 forward solve, the taping forward and its adjoint, the RHS kernel and the tangent-linear pass give the bits they gave before.
 

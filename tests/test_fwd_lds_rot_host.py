@@ -1,4 +1,4 @@
-"""The forward kernels' hybrid hidden layer (mlp_hidden_blk_lds, csrc/hode_device.h: the last K rotations of a layer fetched through
+"""The forward kernels' hybrid hidden layer (mlp_hidden_blk_lds, csrc/hode_mlp.h: the last K rotations of a layer fetched through
 LDS) as hipcc compiles it for gfx950 -- no GPU: csrc/hode_solve_fwd.hip goes to assembly, device code only.
 
 Checks of the code that was written, nothing else: the registers, scratch, occupancy and LDS of the instantiations, and in the

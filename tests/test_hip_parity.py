@@ -35,7 +35,7 @@ def hode():
 
 
 def test_xlane_primitives(hode):
-    """DPP / permlane-swap helpers of csrc/hode_device.h do what their comments say."""
+    """DPP / permlane-swap helpers of csrc/hode_xlane.h do what their comments say."""
     out = hode.selftest_xlane().cpu().numpy()
     lane = np.arange(64)
     v = lane * lane + 1

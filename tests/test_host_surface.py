@@ -454,3 +454,93 @@ __global__ void bad_kernel(float *out, const float *in)
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "dpp_hazard_check.py"), os.path.join(csrc, "hode_solve_fwd.hip"),
                         os.path.join(csrc, "hode_solve_bwd_ws.hip")], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "0 hazard(s)" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def _hipcc():
+    import shutil
+    return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+_CSRC = os.path.join(PKG, "csrc")
+
+
+def _csrc_headers():
+    import glob
+    return sorted(glob.glob(os.path.join(_CSRC, "*.h"))), sorted(glob.glob(os.path.join(_CSRC, "lab", "*.h")))
+
+
+def test_every_kernel_header_compiles_on_its_own():
+    """Each header of csrc/ and csrc/lab/ brings its own includes: it passes the compiler's syntax check as the only file of a
+    translation unit, host and device pass; the lab headers (and the adjoint header, which takes the lab layer forms in with
+    -DHODE_LAB) also with -DHODE_LAB."""
+    import subprocess
+    from concurrent.futures import ThreadPoolExecutor
+    top, lab = _csrc_headers()
+    assert top and lab
+    jobs = [(h, ()) for h in top + lab] + [(h, ("-DHODE_LAB",)) for h in lab + [os.path.join(_CSRC, "hode_adjoint.h")]]
+
+    def check(job):
+        h, extra = job
+        r = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-std=c++17", "-x", "hip", "-fsyntax-only", *extra, h],
+                           capture_output=True, text=True, timeout=600)
+        return h, extra, r.returncode, r.stderr
+    with ThreadPoolExecutor(4) as pool:
+        for h, extra, rc, err in pool.map(check, jobs):
+            assert rc == 0 and "error:" not in err, (h, extra, err[-2000:])
+
+
+def _deps(src, *extra):
+    """the files `src` includes, by the compiler's own dependency output (-MM), as paths relative to csrc/"""
+    import subprocess
+    r = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-std=c++17", "-MM", *extra, os.path.join(_CSRC, src)], cwd=_CSRC,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    words = r.stdout.replace("\\\n", " ").split()
+    return {os.path.relpath(os.path.join(_CSRC, w), _CSRC) for w in words if not w.endswith(":")}
+
+
+def test_translation_units_include_only_their_concern():
+    """The forward solve does not compile the adjoint's building blocks, the C ABI file (host code) no device header, and no
+    source of the product library anything under csrc/lab/."""
+    import glob
+    from concurrent.futures import ThreadPoolExecutor
+    srcs = sorted(os.path.basename(f) for f in glob.glob(os.path.join(_CSRC, "*.hip")))
+    assert "hode_solve_fwd.hip" in srcs and "hode_capi.hip" in srcs
+    with ThreadPoolExecutor(4) as pool:
+        deps = dict(zip(srcs, pool.map(_deps, srcs)))
+    assert "hode_rhs_eval.h" in deps["hode_solve_fwd.hip"] and "hode_adjoint.h" in deps["hode_solve_bwd.hip"]      # the parse sees headers
+    for fwd in ("hode_solve_fwd.hip", "hode_rhs.hip"):
+        assert "hode_adjoint.h" not in deps[fwd], fwd
+    top, _ = _csrc_headers()
+    device_headers = {os.path.basename(h) for h in top} - {"hode_kernels.h"}
+    assert not (deps["hode_capi.hip"] & device_headers), deps["hode_capi.hip"] & device_headers
+    for src, d in deps.items():
+        assert not [f for f in d if f.startswith("lab" + os.sep)], (src, d)
+    # the lab library's forward kernels stay clear of the adjoint header as well
+    for f in sorted(glob.glob(os.path.join(_CSRC, "lab", "hode_solve_fwd_*.hip"))):
+        assert "hode_adjoint.h" not in _deps(os.path.relpath(f, _CSRC), "-DHODE_LAB"), f
+
+
+def test_lab_stamp_follows_the_lab_headers(tmp_path, monkeypatch):
+    """csrc/Makefile stamps hode/lab/libhode_lab.so with its sources INCLUDING csrc/lab/*.h, and hode/_build.py recomputes the same
+    hash: a touched lab header makes the lab library stale and leaves the product library, which never sees it, current."""
+    import shutil
+    from hode import _build
+    assert _build.is_current() and _build.lab_is_current() and _build.lab_source_stamp() == _build.binary_stamp(_build.LAB_SO)
+    pkg = tmp_path / "pkg"
+    shutil.copytree(_CSRC, pkg / "csrc", ignore=shutil.ignore_patterns("_obj", "*.o", ".build.lock"))
+    os.makedirs(tmp_path / "include")
+    shutil.copy(os.path.join(os.path.dirname(PKG), "include", "hode.h"), tmp_path / "include" / "hode.h")
+    os.makedirs(pkg / "hode" / "lab")
+    for so, dst in ((_build.SO, pkg / "hode" / "libhode.so"), (_build.LAB_SO, pkg / "hode" / "lab" / "libhode_lab.so")):
+        shutil.copy(so, dst)
+        shutil.copy(so + ".srcsha", str(dst) + ".srcsha")
+    monkeypatch.setattr(_build, "CSRC", str(pkg / "csrc"))
+    monkeypatch.setattr(_build, "SO", str(pkg / "hode" / "libhode.so"))
+    monkeypatch.setattr(_build, "LAB_SO", str(pkg / "hode" / "lab" / "libhode_lab.so"))
+    assert _build.is_current() and _build.lab_is_current()            # same sources, other place
+    headers = sorted((pkg / "csrc" / "lab").glob("*.h"))
+    assert headers
+    headers[0].write_text(headers[0].read_text() + "\n// touched\n")
+    assert not _build.lab_is_current()
+    assert _build.is_current()

@@ -10,7 +10,7 @@ at 4.2 pipe cycles each with two waves sharing the pipe (2 x 4.2 per instruction
 
     ... python tools/fwd_trace.py --lifetimes [--tape]
 
-The LIFETIME of every wave of the launch instead (hode_device.h, g_wl: entry, end of the weight prologue, grid index T/4, T/2, 3T/4,
+The LIFETIME of every wave of the launch instead (hode_rhs_eval.h, g_wl: entry, end of the weight prologue, grid index T/4, T/2, 3T/4,
 exit, the hardware id of its slot), grouped by SIMD, for B = 2 048 (one round of the chip's wave slots) and 4 096 (the benchmark):
 how far apart the partners of a SIMD finish, how long a SIMD runs one wave only, how long none before the launch ends, and the weight
 prologue of each round.  HODE_LIB names the build, so a library built with -DHODE_FWD_NOPACE gives the picture without the pacing."""

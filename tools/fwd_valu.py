@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Vector instructions per DP5(4) stage of the tuned forward kernels, from the compiler's assembly (static):
 
-    python tools/fwd_valu.py [-DHODE_FINISH_PAIRS ...]
+    python tools/fwd_valu.py [-DHODE_FWD_LDS_ROT=0 ...]
 
 Compiles csrc/hode_solve_fwd.hip for gfx950 with the given extra flags (device code only, to /tmp), finds the accept/reject
 loop of solve_fwd_kernel<float, 4, 0, 2, TAPE, false> (the longest backward branch) and prints the vector-instruction count

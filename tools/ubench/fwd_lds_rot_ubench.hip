@@ -1,5 +1,5 @@
 // The late rotations of a row-block hidden layer through LDS instead of DPP: does it pay?
-// Production form (csrc/hode_device.h mlp_hidden_blk): 2 v_pk_mul + 15 x (v_mov_b32_dpp row_ror:n + 2 v_pk_fma_f32) + finish, the
+// Production form (csrc/hode_mlp.h mlp_hidden_blk): 2 v_pk_mul + 15 x (v_mov_b32_dpp row_ror:n + 2 v_pk_fma_f32) + finish, the
 // accumulators in v[4:7], the moved operand in v8, the input in v10 -- all by name, two asm statements per layer.
 // Hybrid form, K in {4, 8, 12}: the wave writes its input to a private LDS buffer of 4 rows x 48 dwords (row r = its 16 activations
 // twice, at entries j and j + 16: ONE ds_write2_b32, offsets 0 and 16) and fetches the operands of rotations 16-K..15 at the layer's
