@@ -203,9 +203,9 @@ template <bool RELU> __device__ __forceinline__ float mlp_hidden_blk(const f2_t 
     "v_pk_fma_f32 v[6:7], %[wb" #n "], v[8:9], v[6:7] op_sel_hi:[1,0,1]\n\t"
 #define HODE_BK_STEP(n) HODE_BK_MOV(n) HODE_BK_FMA(n)
 #define HODE_BK_W(n) [wa##n] "v"(wp[2 * n]), [wb##n] "v"(wp[2 * n + 1])
-    // (the s_nop 1 predates the merge: with the two products in front of the first move it is one wait state more than needed)
-    asm("s_nop 1\n\t"
-        "v_pk_mul_f32 v[4:5], %[wa0], v[10:11] op_sel_hi:[1,0]\n\t"
+    // (no pad opens the layer: the two products are the two wait states between whatever wrote v10 and its first DPP read.  The
+    //  s_nop 1 that stood here until the stage trim, DESIGN.md section 4.2, was worth 1.4 % of the benchmark launch in the LDS form)
+    asm("v_pk_mul_f32 v[4:5], %[wa0], v[10:11] op_sel_hi:[1,0]\n\t"
         "v_pk_mul_f32 v[6:7], %[wb0], v[10:11] op_sel_hi:[1,0]\n\t"
         HODE_BK_STEP(1) HODE_BK_STEP(2) HODE_BK_STEP(3) HODE_BK_STEP(4) HODE_BK_STEP(5) HODE_BK_STEP(6) HODE_BK_STEP(7) HODE_BK_MOV(8)
         : "=&{v[4:5]}"(a02), "=&{v[6:7]}"(a13), "=&{v8}"(lo)
@@ -287,7 +287,6 @@ __device__ __forceinline__ float mlp_hidden_blk_lds(const f2_t (&wp)[kMaxH / 2],
 #define HODE_BL_WAIT "s_waitcnt lgkmcnt(0)\n\t"
     // (two plain products stand between the layer's producer and the first DPP read of v10, as in mlp_hidden_blk)
 #define HODE_BL_HEAD                                                                                                           \
-    "s_nop 1\n\t"                                                                                                              \
     "v_pk_mul_f32 v[4:5], %[wa0], v[10:11] op_sel_hi:[1,0]\n\t"                                                                \
     "v_pk_mul_f32 v[6:7], %[wb0], v[10:11] op_sel_hi:[1,0]\n\t"
 #define HODE_BL_FINISH                                                                                                         \
@@ -297,13 +296,18 @@ __device__ __forceinline__ float mlp_hidden_blk_lds(const f2_t (&wp)[kMaxH / 2],
     "v_pk_add_f32 v[4:5], v[4:5], v[6:7]\n\t"                                                                                  \
     "s_nop 1\n\t"                                                                                                              \
     "v_permlane32_swap_b32 v4, v5\n\t"                                                                                         \
-    "v_add_f32 v4, v4, v5\n\t"                                                                                                 \
-    "v_add_f32 v4, v4, %[bias]"
+    "v_add_f32 v4, v4, v5\n\t"
+    // The finish's LAST instruction writes v10 and the function returns the low half of the input pair, a read-write operand of the
+    // tail statement: the result stands where the next layer's {v[10:11]} takes its input -- no v_mov_b64 v[10:11], v[4:5] and no
+    // boundary pad between two layers (12 + 12 per DP5(4) step).  Here only: the same in mlp_hidden_blk put 12 B of scratch into
+    // rhs_bwd_kernel<float, 4>.
+#define HODE_BL_END_RELU "v_add_f32 v4, v4, %[bias]\n\tv_max_f32 v10, 0, v4"
+#define HODE_BL_END_LIN "v_add_f32 v10, v4, %[bias]"
 #define HODE_BL_W(n) [wa##n] "v"(wp[2 * n]), [wb##n] "v"(wp[2 * n + 1])
 #define HODE_BL_OUT1 "=&{v[4:5]}"(a02), "=&{v[6:7]}"(a13), "=&{v8}"(lo)
-#define HODE_BL_IO2 "+{v[4:5]}"(a02), "+{v[6:7]}"(a13), "+{v8}"(lo)
+#define HODE_BL_IO2 "+{v[4:5]}"(a02), "+{v[6:7]}"(a13), "+{v8}"(lo), "+{v[10:11]}"(hh)
 #define HODE_BL_IN1 "{v[10:11]}"(hh), [ad] "v"(rot)
-#define HODE_BL_IN2 "{v[10:11]}"(hh), [bias] "v"(bias)
+#define HODE_BL_IN2 [bias] "v"(bias)
 #define HODE_BL_Q(q) [q] "=&v"(q)
 #define HODE_BL_QI(q) [q] "v"(q)
     // one rotation from the HIGH half of the named pair p (v[8:9] or v[10:11]: the lean form fetches into v9 and v11)
@@ -323,11 +327,11 @@ __device__ __forceinline__ float mlp_hidden_blk_lds(const f2_t (&wp)[kMaxH / 2],
 #define HODE_BL_TAIL(RELU_TAIL)                                                                                                \
         asm(HODE_BL_HI(8, "v[8:9]") HODE_BL_HI(9, "v[10:11]") HODE_BL_LDS2(10, 11, q0) HODE_BL_LDS2(12, 13, q1) HODE_BL_LDS2(14, 15, q2) \
             HODE_BL_FINISH RELU_TAIL                                                                                        \
-            : "+{v[4:5]}"(a02), "+{v[6:7]}"(a13)                                                                            \
-            : "{v[8:9]}"(lo2), "{v[10:11]}"(hh), [bias] "v"(bias), HODE_BL_QI(q0), HODE_BL_QI(q1), HODE_BL_QI(q2), HODE_BL_W(8),      \
+            : "+{v[4:5]}"(a02), "+{v[6:7]}"(a13), "+{v[10:11]}"(hh)                                                         \
+            : "{v[8:9]}"(lo2), [bias] "v"(bias), HODE_BL_QI(q0), HODE_BL_QI(q1), HODE_BL_QI(q2), HODE_BL_W(8),      \
               HODE_BL_W(9), HODE_BL_W(10), HODE_BL_W(11), HODE_BL_W(12), HODE_BL_W(13), HODE_BL_W(14), HODE_BL_W(15))
-        if constexpr (RELU) HODE_BL_TAIL("\n\tv_max_f32 v4, 0, v4");
-        else HODE_BL_TAIL("");
+        if constexpr (RELU) HODE_BL_TAIL(HODE_BL_END_RELU);
+        else HODE_BL_TAIL(HODE_BL_END_LIN);
 #undef HODE_BL_TAIL
     } else if constexpr (K == 4) {
         f2_t q0, q1;
@@ -341,8 +345,8 @@ __device__ __forceinline__ float mlp_hidden_blk_lds(const f2_t (&wp)[kMaxH / 2],
         asm(HODE_BL_FMA(11) HODE_BL_LDS2(12, 13, q0) HODE_BL_LDS2(14, 15, q1) HODE_BL_FINISH RELU_TAIL                         \
             : HODE_BL_IO2                                                                                                      \
             : HODE_BL_IN2, HODE_BL_QI(q0), HODE_BL_QI(q1), HODE_BL_W(11), HODE_BL_W(12), HODE_BL_W(13), HODE_BL_W(14), HODE_BL_W(15))
-        if constexpr (RELU) HODE_BL_TAIL("\n\tv_max_f32 v4, 0, v4");
-        else HODE_BL_TAIL("");
+        if constexpr (RELU) HODE_BL_TAIL(HODE_BL_END_RELU);
+        else HODE_BL_TAIL(HODE_BL_END_LIN);
 #undef HODE_BL_TAIL
     } else if constexpr (K == 8) {
         f2_t q0, q1, q2, q3;
@@ -355,8 +359,8 @@ __device__ __forceinline__ float mlp_hidden_blk_lds(const f2_t (&wp)[kMaxH / 2],
             : HODE_BL_IO2                                                                                                      \
             : HODE_BL_IN2, HODE_BL_QI(q0), HODE_BL_QI(q1), HODE_BL_QI(q2), HODE_BL_QI(q3), HODE_BL_W(8), HODE_BL_W(9), HODE_BL_W(10),  \
               HODE_BL_W(11), HODE_BL_W(12), HODE_BL_W(13), HODE_BL_W(14), HODE_BL_W(15))
-        if constexpr (RELU) HODE_BL_TAIL("\n\tv_max_f32 v4, 0, v4");
-        else HODE_BL_TAIL("");
+        if constexpr (RELU) HODE_BL_TAIL(HODE_BL_END_RELU);
+        else HODE_BL_TAIL(HODE_BL_END_LIN);
 #undef HODE_BL_TAIL
     } else {
         f2_t q0, q1, q2, q3, q4, q5;
@@ -370,8 +374,8 @@ __device__ __forceinline__ float mlp_hidden_blk_lds(const f2_t (&wp)[kMaxH / 2],
             : HODE_BL_IO2                                                                                                      \
             : HODE_BL_IN2, HODE_BL_QI(q2), HODE_BL_QI(q3), HODE_BL_QI(q4), HODE_BL_QI(q5), HODE_BL_W(8), HODE_BL_W(9), HODE_BL_W(10),  \
               HODE_BL_W(11), HODE_BL_W(12), HODE_BL_W(13), HODE_BL_W(14), HODE_BL_W(15))
-        if constexpr (RELU) HODE_BL_TAIL("\n\tv_max_f32 v4, 0, v4");
-        else HODE_BL_TAIL("");
+        if constexpr (RELU) HODE_BL_TAIL(HODE_BL_END_RELU);
+        else HODE_BL_TAIL(HODE_BL_END_LIN);
 #undef HODE_BL_TAIL
     }
 #undef HODE_BL_HI
@@ -383,6 +387,8 @@ __device__ __forceinline__ float mlp_hidden_blk_lds(const f2_t (&wp)[kMaxH / 2],
 #undef HODE_BL_OUT1
 #undef HODE_BL_W
 #undef HODE_BL_FINISH
+#undef HODE_BL_END_RELU
+#undef HODE_BL_END_LIN
 #undef HODE_BL_HEAD
 #undef HODE_BL_WAIT
 #undef HODE_BL_RD
@@ -391,10 +397,13 @@ __device__ __forceinline__ float mlp_hidden_blk_lds(const f2_t (&wp)[kMaxH / 2],
 #undef HODE_BL_STEP
 #undef HODE_BL_FMA
 #undef HODE_BL_MOV
-    return a02.x;
+    return hh.x;
 }
 // The forward solve kernels' weight holder: MlpRegs whose hidden layers take the hybrid form (mlp_load and RhsRegs see an MlpRegs)
 template <int NL, int K, bool LEAN = false> struct MlpRegsRot : MlpRegs<float, NL> {
+    // the kernels that had the registers for this layer have the aligned pairs of the packed mechanistic terms too (mech_eval<R, PACK>,
+    // hode_rhs_eval.h); the K = 0 instantiations do not: the taping DP5(4) kernel answers the packed form with 12 B of scratch
+    static constexpr bool kPackMech = true;
     unsigned rot;                     // rot_lane_addr of the wave's buffer
     __device__ __forceinline__ float hidden(int l, float h) const { return mlp_hidden_blk_lds<false, K, LEAN>(this->wh[l], this->b[l + 1], h, rot); }
     __device__ __forceinline__ float hidden_relu(int l, float h) const { return mlp_hidden_blk_lds<true, K, LEAN>(this->wh[l], this->b[l + 1], h, rot); }

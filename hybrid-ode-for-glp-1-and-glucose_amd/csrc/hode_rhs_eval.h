@@ -46,6 +46,22 @@ template <int K> __device__ __forceinline__ float fmac_state(float acc, float Y,
 HODE_FMAC_STATE(0) HODE_FMAC_STATE(1) HODE_FMAC_STATE(2) HODE_FMAC_STATE(3) HODE_FMAC_STATE(4) HODE_FMAC_STATE(5)
 #undef HODE_FMAC_STATE
 template <int K> __device__ __forceinline__ double fmac_state(double acc, double Y, double w) { return rfma(w, lane_bcast(Y, K), acc); }
+// x_K as the factor of ONE product, x_K * v: a broadcast value (the generic path, fp64), or the replicated state itself with the
+// broadcast folded into the multiplication (fp32: v_mul_f32_dpp row_newbcast:K; Y two wait states old, as for fmac_state)
+template <typename R> struct StateVal {
+    R x;
+    __device__ __forceinline__ R times(R v) const { return x * v; }
+};
+template <int K> struct StateDpp {
+    float Y;
+    __device__ __forceinline__ float times(float v) const
+    {
+        static_assert(K == 5, "row_newbcast:5 is the one the right-hand side folds");
+        float out;
+        asm("v_mul_f32_dpp %0, %1, %2 row_newbcast:5 row_mask:0xf bank_mask:0xf" : "=v"(out) : "v"(Y), "v"(v));
+        return out;
+    }
+};
 
 // KK with the eight lanes of stage slot s (lanes 8 s .. 8 s + 7) replaced by F.  fp32: the lane mask 0xff << 8 s is scalar
 // arithmetic and feeds v_cndmask_b32 as an SGPR pair -- (lane >> 3) == s costs a shift and a compare on the vector ALU in
@@ -71,19 +87,38 @@ template <typename R> __device__ __forceinline__ R keep_term(bool sel, R term, R
 // ------------------------------------------------------------------------------------------
 // Mechanistic part (models/ode_core.py:124-153), evaluated redundantly on every lane from the broadcast state; the lane
 // keeps the component of its slot c8 = lane & 7 (GE, slot 4, has no dynamics; slots 6, 7 are padding).
-template <typename R>
-__device__ __forceinline__ R mech_eval(const OdeP<R> &o, R G, R I, R Glu, R GLP1, R FFA, R meal, R gde, int c8)
+// FFA is the factor of one product only: a StateVal, or a StateDpp<5> that reads it out of the replicated state in that product.
+// PACK (fp32): the independent pairs of the terms as packed adds and products -- (u, d1) = (G, GLP1) + (-G_b, EC_50),
+// (v, w) = (I, Glu) + (-I_b, -Glu_b), (q2, q1) = (G, GLP1) * (rcp d2, rcp d1) -- three instructions for six.  Each half rounds exactly
+// like the scalar instruction, and a - b == a + (-b) bit for bit: the kernels stay comparable whichever form they take.
+template <typename R, bool PACK = false, typename FS>
+__device__ __forceinline__ R mech_eval(const OdeP<R> &o, R G, R I, R Glu, R GLP1, const FS &FFA, R meal, R gde, int c8)
 {
     // Every product / sum is written out (fused where one rounding is saved) and contraction is off: the bits do not depend
     // on which kernel this is inlined into (the forward variants are compared bit for bit, tests/test_hip_parity.py).
 #pragma clang fp contract(off)
-    const R u = G - o.G_b, v = I - o.I_b, w = Glu - o.Glu_b;
-    const R Pi = rfma(o.rho, GLP1, R(1));
-    R dI = rfma(Pi * o.a_GI, u, -(o.k_I * v));                                     // ode_core.py:124-125
-    R dGlu = -(o.E_max * rdiv(GLP1, o.EC_50 + GLP1)) * w;                          // :129-130
-    R dGLP1 = rfma(o.V_max, rdiv(G, o.K_m + G), -(o.k_L * GLP1));                  // :134-135
+    R v, w, dI, dGlu, dGLP1;
+    if constexpr (PACK) {
+        static_assert(sizeof(R) == 4, "packed fp32 instructions");
+        const f2_t A = {G, GLP1}, B = {I, Glu};
+        const f2_t ud = A + f2_t{-o.G_b, o.EC_50}, vw = B + f2_t{-o.I_b, -o.Glu_b};
+        v = vw.x, w = vw.y;
+        const f2_t rr = {__builtin_amdgcn_rcpf(o.K_m + G), __builtin_amdgcn_rcpf(ud.y)};
+        const f2_t qq = A * rr;                                                    // (G / (K_m + G), GLP1 / (EC_50 + GLP1))
+        const R Pi = rfma(o.rho, GLP1, R(1));
+        dI = rfma(Pi * o.a_GI, ud.x, -(o.k_I * v));
+        dGlu = -(o.E_max * qq.y) * w;
+        dGLP1 = rfma(o.V_max, qq.x, -(o.k_L * GLP1));
+    } else {
+        const R u = G - o.G_b;
+        v = I - o.I_b, w = Glu - o.Glu_b;
+        const R Pi = rfma(o.rho, GLP1, R(1));
+        dI = rfma(Pi * o.a_GI, u, -(o.k_I * v));                                   // ode_core.py:124-125
+        dGlu = -(o.E_max * rdiv(GLP1, o.EC_50 + GLP1)) * w;                        // :129-130
+        dGLP1 = rfma(o.V_max, rdiv(G, o.K_m + G), -(o.k_L * GLP1));                // :134-135
+    }
     const R k_GE = o.k_GE0 * (R(1) - gde);                                         // :139-140
-    R dFFA = rfma(o.p_9, G, rfma(-o.p_8, I, -o.p_7)) * FFA;                        // :144  (-p7 - p8 I + p9 G) F
+    R dFFA = FFA.times(rfma(o.p_9, G, rfma(-o.p_8, I, -o.p_7)));                   // :144  (-p7 - p8 I + p9 G) F
     R dG = rfma(-k_GE, G, rfma(R(0.005), w, rfma(R(-0.01), v, meal)));             // :148-150
     R r = keep_term(c8 == 0, dG, R(0));
     r = keep_term(c8 == 1, dI, r);
@@ -91,6 +126,10 @@ __device__ __forceinline__ R mech_eval(const OdeP<R> &o, R G, R I, R Glu, R GLP1
     r = keep_term(c8 == 3, dGLP1, r);
     r = keep_term(c8 == 5, dFFA, r);
     return r;
+}
+template <typename R> __device__ __forceinline__ R mech_eval(const OdeP<R> &o, R G, R I, R Glu, R GLP1, R FFA, R meal, R gde, int c8)
+{
+    return mech_eval<R, false>(o, G, I, Glu, GLP1, StateVal<R>{FFA}, meal, gde, c8);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -142,6 +181,9 @@ __device__ __forceinline__ void wl_exit()
 #define HODE_WL_EXIT()
 #define HODE_WL_GRID(k, T)
 #endif
+// weight holders whose kernel takes the packed form of the mechanistic terms (the forward solve kernels choose per instantiation)
+template <typename T, typename = void> struct packs_mech { static constexpr bool value = false; };
+template <typename T> struct packs_mech<T, decltype((void)T::kPackMech)> { static constexpr bool value = T::kPackMech; };
 template <typename R, int NL, bool KEEP, typename WT, typename ACTS = MlpActs<R, NL>>
 __device__ __forceinline__ R rhs_eval(const WT &W, const OdeP<R> &o, R t, R Y, R meal, R tvns,
                                       R gde /* Hill term, 0 without GD */, int lane, ACTS *acts)
@@ -151,10 +193,15 @@ __device__ __forceinline__ R rhs_eval(const WT &W, const OdeP<R> &o, R t, R Y, R
     unsigned long long ft[8] = {};
 #endif
     HODE_FT(0, Y);
-    const R G = state_bcast<0>(Y), I = state_bcast<1>(Y), Glu = state_bcast<2>(Y), GLP1 = state_bcast<3>(Y),
-            FFA = state_bcast<5>(Y);
+    const R G = state_bcast<0>(Y), I = state_bcast<1>(Y), Glu = state_bcast<2>(Y), GLP1 = state_bcast<3>(Y);
     const int c8 = lane & 7;
-    R mech = mech_eval(o, G, I, Glu, GLP1, FFA, meal, gde, c8);
+    // FFA has two readers, both products: fp32 folds its broadcast into each of them (as GE's into its one)
+    constexpr bool kFoldFFA = sizeof(R) == 4;
+    [[maybe_unused]] R FFA = R(0);
+    if constexpr (!kFoldFFA) FFA = state_bcast<5>(Y);
+    R mech;
+    if constexpr (kFoldFFA) mech = mech_eval<R, packs_mech<WT>::value>(o, G, I, Glu, GLP1, StateDpp<5>{Y}, meal, gde, c8);
+    else mech = mech_eval(o, G, I, Glu, GLP1, FFA, meal, gde, c8);
     HODE_FT(6, mech);
     // ---- MLP (models/nn_residual.py:138-147): input row [t, G, I, Glu, GLP1, GE, FFA, glp1:=GLP1, tvns]
     R h = W.b[0];
@@ -164,7 +211,8 @@ __device__ __forceinline__ R rhs_eval(const WT &W, const OdeP<R> &o, R t, R Y, R
     h = rfma(W.w1[3], Glu, h);
     h = rfma(W.w1g, GLP1, h);                    // columns 4 and 7 (both GLP1), folded by the loaders
     h = fmac_state<4>(h, Y, W.w1[5]);            // GE: only the first layer reads it
-    h = rfma(W.w1[6], FFA, h);
+    if constexpr (kFoldFFA) h = fmac_state<5>(h, Y, W.w1[6]);
+    else h = rfma(W.w1[6], FFA, h);
     h = rfma(W.w1[8], tvns, h);
     h = rmax0(h);
     HODE_FT(1, h);

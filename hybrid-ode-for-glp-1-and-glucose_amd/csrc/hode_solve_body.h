@@ -335,9 +335,14 @@ __device__ __forceinline__ void solve_one(const SolveArgs<R> &a, const int b, co
                     if constexpr (kUnrolled) {
                         float K[7];
                         K[0] = KF;
+                        // the stage time stays a vector value: v_fmamk_f32 takes the literal node with h in a VGPR, and its readers (the
+                        // forcing's ts - t0, the first layer's w1[0] * ts) take a VGPR as well as a scalar -- no v_mov of the literal and no
+                        // v_readfirstlane per stage
+                        float hv = h;
+                        asm volatile("" : "+v"(hv));
 #define HODE_DP_STAGE(S)                                                                                                        \
                         Ys = rfma(h, dp54c::stage_sum<S>(K), Y);                                                               \
-                        K[S] = f_at((S) >= 5 ? tn : first_lane(rfma((float)dp54c::C[S], h, tc)), Ys,                            \
+                        K[S] = f_at((S) >= 5 ? tn : rfma((float)dp54c::C[S], hv, tc), Ys,                                        \
                                     ((S) < 6 || fsal_fits) ? rec_at(ns * 6 + (S)) : nullptr);
                         HODE_DP_STAGE(1) HODE_DP_STAGE(2) HODE_DP_STAGE(3) HODE_DP_STAGE(4) HODE_DP_STAGE(5) HODE_DP_STAGE(6)
 #undef HODE_DP_STAGE
