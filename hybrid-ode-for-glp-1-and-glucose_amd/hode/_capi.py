@@ -28,7 +28,8 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_solve_jvp_f32", "hode_solve_jvp_f64",
            "hode_nuts_begin_f32", "hode_nuts_begin_f64", "hode_nuts_pre_f32", "hode_nuts_pre_f64", "hode_nuts_post_f32",
            "hode_nuts_post_f64", "hode_nuts_compact", "hode_nuts_finish_f32", "hode_nuts_finish_f64",
-           "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64", "hode_sobol_indices_f32", "hode_sobol_indices_f64"]
+           "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64", "hode_sobol_indices_f32", "hode_sobol_indices_f64",
+           "hode_pred_fold_f32", "hode_pred_fold_f64", "hode_pred_score_f32", "hode_pred_score_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -440,6 +441,80 @@ def sobol_indices(Y, D, second_order=True, R=100, seed=0, conf_z=1.9599639845400
         C.c_int(int(R)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_double(conf_z), _ptr(out["S1"]), _ptr(out["ST"]), _ptr(out["S2"]),
         _ptr(out["S1_conf"]), _ptr(out["ST_conf"]), _ptr(out["S2_conf"]), _ptr(out["variance"])), "hode_sobol_indices")
     return out
+
+
+PRED_MAX_BINS, PRED_FIXED_COLS, PRED_SCORE_BLOCKS = 32, 16, 128
+PRED_STATE = ("n", "mean", "m2", "pit", "lmax", "lsum")
+
+
+def pred_state(N, device):
+    """A fresh running state of N entries (include/hode.h "Posterior-predictive summaries"): all zero, lmax = -inf."""
+    z = lambda: torch.zeros(N, dtype=torch.float64, device=device)                               # noqa: E731
+    return {"n": torch.zeros(N, dtype=torch.int32, device=device), "mean": z(), "m2": z(), "pit": z(),
+            "lmax": torch.full((N,), float("-inf"), dtype=torch.float64, device=device), "lsum": z()}
+
+
+def _pred_check_state(state, N, what):
+    for k in PRED_STATE:
+        t = state[k]
+        if t.dtype != (torch.int32 if k == "n" else torch.float64) or t.numel() != N or not t.is_contiguous() or not t.is_cuda:
+            raise HodeError(f"{what}: state[{k!r}] must be a contiguous device tensor of {N} {'int32' if k == 'n' else 'float64'}")
+
+
+def pred_fold(y, state, obs=None, mask=None, sigma=None, status=None):
+    """Fold the draws y [n_draws, ...] (N entries each, fp32 or fp64, used where it lies when its rows are dense) into `state`
+    (pred_state) in draw order; obs [N] in y's dtype and mask uint8 [N] or None; sigma fp64 [n_draws, 6] on the device or None;
+    status int32 [n_draws, n_traj] or None (a non-zero entry skips that draw's trajectory)."""
+    _need_gpu(y)
+    S = y.shape[0]
+    N = state["n"].numel()
+    if y.dim() < 2 or y.numel() != S * N:
+        raise HodeError(f"pred_fold: y must be [n_draws, {N} entries]")
+    if not (y[0].is_contiguous() and (S == 1 or y.stride(0) == N)):
+        y = y.contiguous()
+    _pred_check_state(state, N, "pred_fold")
+    row_len = N
+    if obs is not None and (obs.dtype != y.dtype or obs.numel() != N or not obs.is_contiguous() or obs.device != y.device):
+        raise HodeError("pred_fold: obs must be a contiguous device tensor of N entries in y's dtype")
+    if mask is not None and (obs is None or mask.dtype != torch.uint8 or mask.numel() != N or not mask.is_contiguous()):
+        raise HodeError("pred_fold: mask must be uint8 with the shape of obs")
+    if sigma is not None:
+        sigma = sigma.to(device=y.device, dtype=torch.float64).contiguous()
+        if tuple(sigma.shape) != (S, 6):
+            raise HodeError("pred_fold: sigma must be [n_draws, 6]")
+    if status is not None:
+        status = status.to(device=y.device, dtype=torch.int32).contiguous()
+        if status.dim() != 2 or status.shape[0] != S or status.shape[1] < 1 or N % status.shape[1]:
+            raise HodeError("pred_fold: status must be [n_draws, n_traj] with n_traj dividing N")
+        row_len = N // status.shape[1]
+    _check(getattr(load(), f"hode_pred_fold_{_sfx(y.dtype)}")(
+        _stream(), C.c_int(S), C.c_int64(N), _ptr(y), _ptr(obs), _ptr(mask), _ptr(sigma), _ptr(status), C.c_int64(row_len),
+        *[_ptr(state[k]) for k in PRED_STATE]), "hode_pred_fold")
+
+
+def pred_score(state, dtype, obs=None, mask=None, extra_var=None, thr=(0.0,)):
+    """Score a finished state: returns (mean, sd, pit) [N] in `dtype` and the table fp64 [6, PRED_FIXED_COLS + 2 len(thr)] of
+    include/hode.h; extra_var six host floats or None, thr the host thresholds of the calibration counts."""
+    N = state["n"].numel()
+    _need_gpu(state["n"])
+    _pred_check_state(state, N, "pred_score")
+    dev = state["n"].device
+    nb = len(thr)
+    if not 1 <= nb <= PRED_MAX_BINS:
+        raise HodeError(f"pred_score: {nb} bins, the kernel takes 1..{PRED_MAX_BINS} (HODE_PRED_MAX_BINS)")
+    if obs is not None and (obs.dtype != dtype or obs.numel() != N or not obs.is_contiguous() or obs.device != dev):
+        raise HodeError("pred_score: obs must be a contiguous device tensor of N entries in the working dtype")
+    if mask is not None and (obs is None or mask.dtype != torch.uint8 or mask.numel() != N or not mask.is_contiguous()):
+        raise HodeError("pred_score: mask must be uint8 with the shape of obs")
+    K = PRED_FIXED_COLS + 2 * nb
+    out = [torch.empty(N, dtype=dtype, device=dev) for _ in range(3)]
+    table = torch.empty(6, K, dtype=torch.float64, device=dev)
+    work = torch.empty(PRED_SCORE_BLOCKS * 6 * K, dtype=torch.float64, device=dev)
+    _check(getattr(load(), f"hode_pred_score_{_sfx(dtype)}")(
+        _stream(), C.c_int64(N), *[_ptr(state[k]) for k in PRED_STATE], _ptr(obs), _ptr(mask), _six(extra_var),
+        (C.c_double * nb)(*[float(x) for x in thr]), C.c_int(nb), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(table), _ptr(work)),
+        "hode_pred_score")
+    return out[0], out[1], out[2], table
 
 
 def hmc_refresh(C_, D, ld, seed, it, jitter, minv, log_eps, z, g, U, p, z0, g0, U0, ke0, eps, failed):

@@ -274,7 +274,8 @@ class HMCResult:
     shaped [chains, draws, ...]; `flat()`: the same as [chains * draws, ...] (what reference posterior_summary takes);
     `stats`: accept_prob / log_posterior / divergent / failed_solve [chains, draws], step_size [chains], inv_mass [D];
     `rhat()` / `ess()`: split R-hat and multi-chain bulk ESS of every coordinate; `predict(...)`: posterior predictive;
-    `noise_sigma(...)`: draws of the observation noise (inferred with noise="marginal", else the fixed values)."""
+    `noise_sigma(...)`: draws of the observation noise (inferred with noise="marginal", else the fixed values);
+    `predictive_summary(...)`: the posterior predictive folded into per-entry summaries and scored (inference/predictive.py)."""
 
     def __init__(self, draws, ode_names, nn_names, stats, model=None, ode_base=None, nn_base=None, observation=None, data=None):
         self.draws = draws                          # [C, n, D] natural coordinates (device or CPU tensor)
@@ -369,6 +370,26 @@ class HMCResult:
             gen = torch.Generator(device=y.device).manual_seed(int(seed) + 1)
             y = y + sig.view(-1, 1, 1, 6) * torch.randn(y.shape, dtype=y.dtype, device=y.device, generator=gen)
         return y.to(self.model.device)
+
+    def predictive_summary(self, batch=None, thin=1, observation_noise=True, seed=0, n_bins=10, max_bytes=None, solver="dopri5",
+                           rtol=1e-6, atol=1e-8):
+        """The posterior predictive of the kept draws (every `thin`-th of each chain, in `predict`'s order) on `batch` (default:
+        the run's) as a `PredictiveSummary`: mean / std / PIT per entry and the scores against the batch's observations, folded
+        piece by piece under max_bytes of trajectories instead of held as `predict`'s [n_draws, B, T, 6] block.
+        observation_noise=True scores the predictive of the OBSERVATIONS: the draws of `noise_sigma(batch, thin, seed)` (the
+        run's fixed values, or with noise="marginal" the inferred ones) enter the PIT, the log density and, by the law of total
+        variance, std.  Serves run_hmc and run_nuts alike (both return this class)."""
+        from inference import predictive as PR
+        if self.model is None:
+            raise ValueError("this result carries no model (built from arrays)")
+        batch = self.data if batch is None else batch
+        if batch is None:
+            raise ValueError("predictive_summary needs a batch: the run had none")
+        S, nn_flat, ode_vec = self._param_sets(thin)
+        sigma = self.noise_sigma(batch, thin, seed, solver, rtol, atol) if observation_noise else None
+        return PR.predictive_summary(self.model, (nn_flat.view(S, -1), ode_vec.view(S, 17)), batch, sigma=sigma, n_bins=n_bins,
+                                     max_bytes=PR._DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, solver=solver, rtol=rtol,
+                                     atol=atol)
 
     def _solve_draws(self, initial_state, t_span, external_inputs, thin, solver, rtol, atol):
         """[n_draws, B, T, 6] on the compute device."""

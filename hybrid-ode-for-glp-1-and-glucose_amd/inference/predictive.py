@@ -1,0 +1,252 @@
+"""Posterior-predictive summaries and their scores on the GPU, without the stack of draws (csrc/hode_predictive.hip;
+include/hode.h, "Posterior-predictive summaries").
+
+`HMCResult.predict` and `VariationalInference.posterior_predictive` hold every draw's trajectories, [draws, B, T, 6], to reduce
+them to a mean and a standard deviation per entry.  Here the draws are FOLDED into a per-entry running state as they are
+produced (`PredictiveAccumulator.fold`: Welford's update, the predictive CDF at the observation, a streaming log-sum-exp of
+the pointwise log density), a piece of draws at a time, so memory depends on one piece and not on all of them; `finish` scores
+the state against the data in one deterministic pass and `PredictiveSummary.metrics()` names the sums.
+
+Folding the same draws in any split into consecutive `fold` calls gives bit-identical state (the kernel takes the draws one at
+a time in draw order and the state is fp64 in memory as in registers), so `max_bytes` changes memory and nothing else."""
+import math
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+import hode
+
+__all__ = ["PredictiveAccumulator", "PredictiveSummary", "predictive_summary", "cut_draws", "half_normal_thresholds", "STATE_NAMES",
+           "TABLE_COLUMNS"]
+
+STATE_NAMES = ("glucose", "insulin", "glucagon", "glp1", "ge", "ffa")
+# the fixed columns of the score table (include/hode.h); the n_bins threshold counts and the n_bins PIT counts follow
+TABLE_COLUMNS = ("count", "sum_sq_err", "sum_abs_err", "sum_obs", "sum_obs_sq", "count_unc", "sum_sd", "sum_norm_err", "sum_interval_score",
+                 "cover_50", "cover_80", "cover_90", "cover_95", "sum_crps", "sum_lppd", "count_lppd")
+_DEFAULT_MAX_BYTES = 256 << 20
+
+
+def half_normal_thresholds(n_bins: int) -> List[float]:
+    """The exact thresholds of the calibration curve: t_j with P(|Z| <= t_j) = j / n_bins, j = 0 .. n_bins - 1, i.e.
+    sqrt(2) erfinv(j / n_bins).  (The reference estimates each from 10 000 fresh |randn| per call, eval/evaluate.py:134-138, so
+    its ECE changes from call to call; these are what its percentiles converge to.)"""
+    c = torch.arange(n_bins, dtype=torch.float64) / n_bins
+    return (math.sqrt(2.0) * torch.erfinv(c)).tolist()
+
+
+def cut_draws(n_draws: int, bytes_per_draw: int, max_bytes: int) -> List[Tuple[int, int]]:
+    """Cut draws 0 .. n_draws - 1 into consecutive pieces [lo, hi) whose trajectories fit max_bytes (at least one draw per
+    piece): every draw once, in order."""
+    if n_draws < 0 or bytes_per_draw < 1:
+        raise ValueError("cut_draws: n_draws >= 0 and bytes_per_draw >= 1")
+    per = max(1, int(max_bytes) // int(bytes_per_draw))
+    return [(lo, min(lo + per, n_draws)) for lo in range(0, n_draws, per)]
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise hode.HodeError("predictive summaries need a HIP device: the fold and score kernels have no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+class PredictiveSummary:
+    """What `PredictiveAccumulator.finish` returns: `mean`, `std`, `pit` (working precision) and `n` (int32), all [B, T, 6] on
+    the device -- std is unbiased like torch.std plus the mean noise variance, NaN where fewer than two draws were folded; pit is
+    the mean predictive CDF at the observation, NaN where unobserved -- `table` (fp64 numpy [6, 16 + 2 n_bins], the per-state
+    sums of include/hode.h, columns TABLE_COLUMNS then the threshold counts then the PIT histogram) and `metrics()`."""
+
+    def __init__(self, mean, std, pit, n, table, thresholds):
+        self.mean, self.std, self.pit, self.n = mean, std, pit, n
+        self.table = np.asarray(table, dtype=np.float64)
+        self.thresholds = list(thresholds)
+        self.n_bins = len(self.thresholds)
+
+    def metrics(self) -> Dict[str, Union[float, np.ndarray]]:
+        return table_metrics(self.table, self.n_bins)
+
+
+def table_metrics(table: np.ndarray, n_bins: int) -> Dict[str, Union[float, np.ndarray]]:
+    """The scores of a table [6, 16 + 2 n_bins] (tables of several batches add): every key pooled over the states -- from the
+    pooled sums, e.g. rmse = sqrt(sum sum e^2 / sum count), what the reference's flatten() computes -- and per state under
+    `<key>_per_state` (arrays of 6).  rmse, mae, target_std (unbiased), count; over the entries with at least two draws: ece,
+    msis, sharpness, coverage_50 / 80 / 90 / 95, mean_normalized_error, crps, pit_histogram (fractions, [n_bins]); lppd (the SUM
+    of the log pointwise predictive densities) where observation noise defined one.  A state observed nowhere, or a score with
+    nothing to average, is NaN: nothing raises or divides by zero."""
+    t = np.asarray(table, dtype=np.float64)
+    col = {name: i for i, name in enumerate(TABLE_COLUMNS)}
+    F = len(TABLE_COLUMNS)
+    conf = np.arange(n_bins) / n_bins
+
+    def scores(r):                                     # r: [..., K] sums of one state or of all of them
+        nan = np.full(r.shape[:-1], np.nan)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ce, cu, cl = r[..., col["count"]], r[..., col["count_unc"]], r[..., col["count_lppd"]]
+            over = lambda name, c: np.where(c > 0, r[..., col[name]] / np.where(c > 0, c, 1.0), nan)          # noqa: E731
+            var = (r[..., col["sum_obs_sq"]] - r[..., col["sum_obs"]] ** 2 / np.where(ce > 0, ce, 1.0)) / np.where(ce > 1, ce - 1.0, 1.0)
+            freq = r[..., F:F + n_bins] / np.where(cu > 0, cu, 1.0)[..., None]
+            out = {
+                "count": ce,
+                "rmse": np.sqrt(over("sum_sq_err", ce)),
+                "mae": over("sum_abs_err", ce),
+                "target_std": np.where(ce > 1, np.sqrt(np.maximum(var, 0.0)), nan),
+                "ece": np.where(cu > 0, np.mean(np.abs(conf - freq), axis=-1), nan),
+                "msis": over("sum_interval_score", cu),
+                "sharpness": over("sum_sd", cu),
+                "coverage_50": over("cover_50", cu), "coverage_80": over("cover_80", cu), "coverage_90": over("cover_90", cu),
+                "coverage_95": over("cover_95", cu),
+                "mean_normalized_error": over("sum_norm_err", cu),
+                "crps": over("sum_crps", cu),
+                "lppd": np.where(cl > 0, r[..., col["sum_lppd"]], nan),
+                "pit_histogram": np.where((cu > 0)[..., None], r[..., F + n_bins:F + 2 * n_bins] / np.where(cu > 0, cu, 1.0)[..., None],
+                                          np.nan),
+            }
+        return out
+    pooled, per = scores(t.sum(0)), scores(t)
+    out = {k: (v if v.ndim else float(v)) for k, v in pooled.items()}
+    out.update({f"{k}_per_state": v for k, v in per.items()})
+    return out
+
+
+class PredictiveAccumulator:
+    """The running state of n_traj x T x 6 entries on the device.  `fold(y, sigma=None, status=None)` adds draws,
+    `finish(n_bins=10)` scores them.  observations [n_traj, T, 6] (NaN = missing) and observation_mask (bool, same shape) as in
+    inference/observation.py; without observations only mean / std / n are produced and the table is empty."""
+
+    def __init__(self, n_traj: int, T: int, observations=None, observation_mask=None, dtype=torch.float32):
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype must be torch.float32 or torch.float64")
+        if n_traj < 1 or T < 1:
+            raise ValueError("n_traj and T must be >= 1")
+        if observation_mask is not None and observations is None:
+            raise ValueError("observation_mask needs observations")
+        self.n_traj, self.T, self.dtype = int(n_traj), int(T), dtype
+        self.N = self.n_traj * self.T * 6
+        dev = self.device = _device()
+        self.obs = self.mask = None
+        if observations is not None:
+            obs = torch.as_tensor(observations)
+            if tuple(obs.shape) != (self.n_traj, self.T, 6):
+                raise ValueError(f"observations must be [{self.n_traj}, {self.T}, 6]")
+            self.obs = obs.to(dev, dtype).reshape(-1).contiguous()
+            if observation_mask is not None:
+                m = torch.as_tensor(observation_mask)
+                if m.shape != obs.shape:
+                    raise ValueError("observation_mask must have the shape of observations")
+                self.mask = m.to(dev).ne(0).to(torch.uint8).reshape(-1).contiguous()
+        self.state = hode.capi.pred_state(self.N, dev)
+        self._var_sum = torch.zeros(6, dtype=torch.float64, device=dev)       # sum over the folded draws of sigma_k^2
+        self.n_folded = 0
+
+    @classmethod
+    def from_moments(cls, predictions, uncertainties, observations, observation_mask=None, dtype=None):
+        """An accumulator whose state IS the given mean and standard deviation ([B, T, 6] each; two pseudo-draws per entry, so
+        std = uncertainties exactly): what the metric functions of eval/evaluate.py score.  uncertainties=None: one draw."""
+        p = torch.as_tensor(predictions)
+        if p.dim() != 3 or p.shape[2] != 6:
+            raise ValueError("predictions must be [batch, time, 6]")
+        dtype = dtype or (torch.float64 if p.dtype == torch.float64 else torch.float32)
+        acc = cls(p.shape[0], p.shape[1], observations, observation_mask, dtype)
+        acc.state["mean"].copy_(p.to(acc.device, torch.float64).reshape(-1))
+        if uncertainties is None:
+            acc.state["n"].fill_(1)
+        else:
+            u = torch.as_tensor(uncertainties)
+            if u.shape != p.shape:
+                raise ValueError("uncertainties must have the shape of predictions")
+            acc.state["n"].fill_(2)
+            acc.state["m2"].copy_(u.to(acc.device, torch.float64).reshape(-1) ** 2)
+        return acc
+
+    def _sigma(self, sigma, S):
+        if sigma is None:
+            return None
+        s = torch.as_tensor(sigma, dtype=torch.float64).to(self.device)
+        if s.dim() == 0 or s.numel() == 1:
+            s = s.reshape(1, 1).expand(S, 6)
+        elif s.dim() == 1 and s.numel() == 6:
+            s = s.reshape(1, 6).expand(S, 6)
+        if tuple(s.shape) != (S, 6) or not bool((s >= 0).all()):
+            raise ValueError("sigma must be non-negative: a scalar, one value per state or [n_draws, 6]")
+        return s.contiguous()
+
+    def fold(self, y, sigma=None, status=None):
+        """y: [n_draws, n_traj, T, 6] (or [n_traj, T, 6]: one draw) on the device; sigma: the observation noise of the draws,
+        a scalar, six values or [n_draws, 6]; status: int [n_draws, n_traj], the solve statuses (non-zero: that trajectory of that
+        draw is skipped whole; a non-finite y is skipped for its entry).  Returns self."""
+        y = torch.as_tensor(y)
+        if y.dim() == 3:
+            y = y.unsqueeze(0)
+        if y.dim() != 4 or tuple(y.shape[1:]) != (self.n_traj, self.T, 6):
+            raise ValueError(f"y must be [n_draws, {self.n_traj}, {self.T}, 6]")
+        hode.capi._need_gpu(y)
+        S = y.shape[0]
+        if y.dtype != self.dtype:
+            y = y.to(self.dtype)
+        sig = self._sigma(sigma, S)
+        if status is not None:
+            status = torch.as_tensor(status).reshape(S, self.n_traj)
+        hode.capi.pred_fold(y.reshape(S, self.N) if y.is_contiguous() else y, self.state, self.obs, self.mask, sig, status)
+        if sig is not None:
+            self._var_sum += (sig * sig).sum(0)
+        self.n_folded += S
+        return self
+
+    def finish(self, n_bins: int = 10) -> PredictiveSummary:
+        if not 1 <= int(n_bins) <= hode.capi.PRED_MAX_BINS:
+            raise ValueError(f"n_bins must lie in 1..{hode.capi.PRED_MAX_BINS}")
+        thr = half_normal_thresholds(int(n_bins))
+        extra = (self._var_sum / max(self.n_folded, 1)).tolist()
+        mean, sd, pit, table = hode.capi.pred_score(self.state, self.dtype, self.obs, self.mask, extra, thr)
+        shape = (self.n_traj, self.T, 6)
+        return PredictiveSummary(mean.view(shape), sd.view(shape), pit.view(shape), self.state["n"].view(shape).clone(),
+                                 table.cpu().numpy(), thr)
+
+
+def _rep_inputs(S, x0, t_span, external_inputs):
+    """The batch repeated for S parameter sets, as HybridODENN.forward_param_sets lays it out."""
+    rep = lambda v: torch.as_tensor(v).repeat(*([S] + [1] * (torch.as_tensor(v).dim() - 1)))                  # noqa: E731
+    t = torch.as_tensor(t_span)
+    u = {}
+    for k, v in (external_inputs or {}).items():
+        big = v is not None and torch.as_tensor(v).dim() >= 1 and torch.as_tensor(v).numel() > 1
+        u[k] = rep(v) if big else v
+    return x0.repeat(S, 1), (rep(t) if t.dim() == 2 else t), u
+
+
+def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None, n_bins: int = 10,
+                       max_bytes: int = _DEFAULT_MAX_BYTES, solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8,
+                       dtype=torch.float32) -> PredictiveSummary:
+    """The posterior-predictive summary of `draws` on `batch` {initial_state, time_points[, observations, observation_mask,
+    external_inputs]}.  draws: a list of named parameter overrides (what `variational_params.sample` and `forward_param_sets`
+    take), or a pair (nn_flat [S, P], ode_vec [S, 17]) of parameter tensors.  sigma: the observation noise, None, a scalar, six
+    values or one row of six per draw.  The draws are cut into pieces whose trajectories fit max_bytes (`cut_draws`), each piece
+    is ONE batched solve (no tape) and is folded with the solve's statuses before the next one starts: no more than one
+    piece of trajectories exists at a time, and the result does not depend on the cut."""
+    from models.hybrid_ode_nn import _compute_device
+    dev = _compute_device()
+    x0 = batch["initial_state"]
+    x0 = x0.unsqueeze(0) if x0.dim() == 1 else x0
+    B = x0.shape[0]
+    t = torch.as_tensor(batch["time_points"])
+    T = t.shape[-1]
+    named = not (isinstance(draws, tuple) and len(draws) == 2 and isinstance(draws[0], torch.Tensor))
+    S = len(draws) if named else draws[0].shape[0]
+    acc = PredictiveAccumulator(B, T, batch.get("observations"), batch.get("observation_mask"), dtype)
+    sig = acc._sigma(sigma, S)
+    for lo, hi in cut_draws(S, B * T * 6 * 4, max_bytes):                         # (the solve's trajectories are fp32)
+        n = hi - lo
+        if named:
+            flat = [model._params_on(dev, p) for p in draws[lo:hi]]
+            nn_flat, ode_vec = torch.cat([f[0] for f in flat]), torch.cat([f[1] for f in flat])
+        else:
+            nn_flat = draws[0][lo:hi].to(dev, torch.float32).reshape(-1).contiguous()
+            ode_vec = draws[1][lo:hi].to(dev, torch.float32).reshape(-1).contiguous()
+        xs, ts, us = _rep_inputs(n, x0, t, batch.get("external_inputs"))
+        with torch.no_grad():
+            y = model._solve(xs, ts, us, solver, rtol, atol, n_sets=n, nn_flat=nn_flat, ode_vec=ode_vec, differentiable=False)
+        info = model.last_solve_info
+        model._warn_failures(info)
+        acc.fold(y.view(n, B, T, 6), None if sig is None else sig[lo:hi], info["status"].view(n, B))
+        del y
+    return acc.finish(n_bins)

@@ -518,6 +518,78 @@ int hode_sobol_indices_f64(void *stream, int N, int D, int M, const double *Y, i
                            double conf_z, double *S1, double *ST, double *S2, double *S1_conf, double *ST_conf, double *S2_conf,
                            double *variance);
 
+/* =====================================================================================================
+ * Posterior-predictive summaries (inference/predictive.py, eval/evaluate.py): what the reference's eval/evaluate.py
+ * computes from a stack of predictive draws -- mean(0), std(0), RMSE / MAE, the calibration scores -- without the stack.
+ *
+ * An ENTRY is one element i < N of a [n_traj][T][6] block, N = n_traj * T * 6; its state is i % 6.  Entry i is OBSERVED as
+ * in hode_obs_nll_sets_*: obs[i] finite and, with a mask (uint8[N], NULL = finiteness only), mask[i] != 0; no arithmetic
+ * touches the obs value of an unobserved entry.
+ *
+ * The running state of the entries, DEVICE memory the caller owns, N elements each:
+ *   n      int32   draws folded so far
+ *   mean   double  running mean
+ *   m2     double  running sum of squared deviations from the mean
+ *   pit    double  sum over the folded draws of the predictive CDF at the observation
+ *   lmax   double  running maximum of the streaming log-sum-exp of log N(obs | y, sigma_k^2)
+ *   lsum   double  running sum of the same: sum_s exp(lp_s - lmax)
+ * A fresh state is all zero except lmax = -infinity.
+ *
+ * hode_pred_fold_* folds n_draws more draws y[n_draws][N] into the state, ONE AT A TIME IN DRAW ORDER, per entry:
+ *   skip the draw when status[s][i / row_len] != 0 (status: int32[n_draws][N / row_len], NULL = all fine; rows of y after a
+ *   failed solve are zero and must not be averaged in) or when y is not finite; else
+ *     n += 1;  d = y - mean;  mean += d / n;  m2 += d * (y - mean)                                     (Welford)
+ *   and, for an observed entry,
+ *     with sigma (double[n_draws][6], DEVICE; NULL = no observation noise) and sigma[s][k] > 0:
+ *       z = (obs - y) / sigma;  pit += Phi(z);  lp = -z^2 / 2 - log sigma - log(2 pi) / 2;
+ *       lp > lmax ?  (lsum = lsum * exp(lmax - lp) + 1, lmax = lp)  :  lsum += exp(lp - lmax)
+ *     else  pit += 1 if y < obs, 1/2 if y == obs, 0 otherwise;  lmax, lsum stay.
+ *   obs NULL: nothing is observed, and pit, lmax, lsum are not written at all.
+ * Each update is computed in fp64 without contraction and does not depend on where a call begins or ends, and the state is
+ * fp64 in memory as in registers: folding S draws in one call and folding the same draws in ANY split into consecutive calls
+ * give bit-identical state.  A lane owns one entry (no reduction, no atomics): the same call gives the same bits.
+ * Unaligned pointers and any N are fine (a wave reads 64 consecutive reals of a draw).
+ * HODE_EINVAL: n_draws < 0, N < 6 or N % 6 != 0, a NULL state pointer, y NULL with n_draws > 0, a mask without obs, with
+ * status a row_len that is no multiple of 6 or does not divide N.  n_draws == 0 is a no-op.
+ *
+ * hode_pred_score_* reads a finished state and writes, in the working precision,
+ *   out_mean = mean (NaN where n == 0),  out_sd = sqrt(m2 / (n - 1) + extra_var[k]) (NaN where n < 2),
+ *   out_pit = pit / n (NaN where n < 2 or the entry is unobserved)
+ * -- extra_var: HOST double[6] (NULL = 0), the mean over the draws of sigma_k^2 (law of total variance) -- and
+ * table: double[6][K], K = HODE_PRED_FIXED_COLS + 2 * n_bins, per-state sums over the OBSERVED entries, with e = mean - obs,
+ * u = |e| / (sd + 1e-6), everything from the fp64 state:
+ *   over n >= 1:   0 count   1 sum e^2   2 sum |e|   3 sum obs   4 sum obs^2
+ *   over n >= 2:   5 count   6 sum sd   7 sum u
+ *                  8 sum of the 95 % interval score: (hi - lo) + (2 / 0.05) ((lo - obs)+ + (obs - hi)+), lo, hi = mean -+ 1.96 sd
+ *                  9..12 counts of lo <= obs <= hi at 50 / 80 / 90 / 95 % (z = 0.6744897501960817, 1.2815515655446004,
+ *                        1.6448536269514722, 1.96; inclusive bounds)
+ *                  13 sum of the Gaussian CRPS  sd (w (2 Phi(w) - 1) + 2 phi(w) - 1 / sqrt(pi)), w = (obs - mean) / sd (|e| at sd = 0)
+ *                  14 sum of the log pointwise predictive density lmax + log(lsum / n) over the entries with lsum > 0,  15 their count
+ *                  16 .. 16 + n_bins - 1            counts of u <= thr[j]   (thr: HOST double[n_bins])
+ *                  16 + n_bins .. 16 + 2 n_bins - 1 PIT histogram: counts of min(floor(n_bins pit / n), n_bins - 1) == j
+ * Reduction in a fixed order: lane sums, block sums (a butterfly inside each wave, then the four wave sums in order), one
+ * partial row per workgroup in work (DEVICE double[HODE_PRED_SCORE_BLOCKS * 6 * K], scratch space), then one pass that adds
+ * the rows in index order; the two histograms are integer counts.  The same call gives the same bits.  Unaligned pointers
+ * and any N are fine (16-byte accesses, twelve entries per lane, when N % 4 == 0 and every pointer allows them).
+ * HODE_EINVAL: N < 6 or N % 6 != 0, n_bins outside 1..HODE_PRED_MAX_BINS, a NULL among the state, thr, the outputs, table
+ * and work, a mask without obs.  obs NULL: nothing is observed (an all-zero table).
+ * ===================================================================================================== */
+#define HODE_PRED_MAX_BINS 32
+#define HODE_PRED_FIXED_COLS 16
+#define HODE_PRED_SCORE_BLOCKS 128
+int hode_pred_fold_f32(void *stream, int n_draws, int64_t N, const float *y, const float *obs, const uint8_t *mask, const double *sigma,
+                       const int32_t *status, int64_t row_len, int32_t *n, double *mean, double *m2, double *pit, double *lmax,
+                       double *lsum);
+int hode_pred_fold_f64(void *stream, int n_draws, int64_t N, const double *y, const double *obs, const uint8_t *mask, const double *sigma,
+                       const int32_t *status, int64_t row_len, int32_t *n, double *mean, double *m2, double *pit, double *lmax,
+                       double *lsum);
+int hode_pred_score_f32(void *stream, int64_t N, const int32_t *n, const double *mean, const double *m2, const double *pit,
+                        const double *lmax, const double *lsum, const float *obs, const uint8_t *mask, const double *extra_var,
+                        const double *thr, int n_bins, float *out_mean, float *out_sd, float *out_pit, double *table, double *work);
+int hode_pred_score_f64(void *stream, int64_t N, const int32_t *n, const double *mean, const double *m2, const double *pit,
+                        const double *lmax, const double *lsum, const double *obs, const uint8_t *mask, const double *extra_var,
+                        const double *thr, int n_bins, double *out_mean, double *out_sd, double *out_pit, double *table, double *work);
+
 #ifdef __cplusplus
 }
 #endif
