@@ -74,19 +74,23 @@ template <typename R, int NL, typename WT> struct RhsRegs {
 
 // en^(-1/5) for the step-size factor (scipy/integrate/_ivp/rk.py:150-176).  fp32: v_log_f32 / v_exp_f32 as they are (the
 // library forms wrap each in a denormal-range rescaling, ~8 instructions; a denormal en gives the factor its cap, 10).
-template <typename R> __device__ __forceinline__ float pow_m02(float en)
+// fp64: the controller runs in double like the oracle's (scipy's): in float its step sizes were 1e-7 off the oracle's with equal
+// step counts, and d/d tVNS -- 1e4 times as sensitive to the step sizes as every other gradient -- 1e-7 off the oracle's adjoint
+// (tests/test_input_grads_enum_gpu.py).
+template <typename R> using CtlT = std::conditional_t<sizeof(R) == 4, float, double>;
+template <typename R> __device__ __forceinline__ CtlT<R> pow_m02(CtlT<R> en)
 {
     if constexpr (sizeof(R) == 4) return __builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf(en));
-    else return __builtin_exp2f(-0.2f * __builtin_log2f(en));
+    else return pow(en, -0.2);
 }
 
 // sqrt(sum / 6): the RMS norm of the step controller (scipy/integrate/_ivp/common.py:63-66).  The fp32 instantiation takes
 // v_sqrt_f32 and a multiplication (1 ulp each) instead of the IEEE square root and division hipcc expands to ~25
 // instructions per step; the fp64 parity instantiation keeps the exact forms.
-template <typename R> __device__ __forceinline__ float rms6(float sum)
+template <typename R> __device__ __forceinline__ CtlT<R> rms6(CtlT<R> sum)
 {
     if constexpr (sizeof(R) == 4) return __builtin_amdgcn_sqrtf(sum * (1.0f / 6.0f));
-    else return sqrtf(sum / 6.0f);
+    else return sqrt(sum / 6.0);
 }
 
 // Dormand-Prince 5(4) as compile-time constants (the values of kTableau[HODE_METHOD_DP54], hode_tableau.h): the fp32 solve unrolls its
@@ -301,6 +305,7 @@ __device__ __forceinline__ void solve_one(const SolveArgs<R> &a, const int b, co
                 const R K1 = f_at(t0, Y, a.max_steps > 0 ? rec_at(0) : nullptr);
                 const R sc = (c8 < 6) ? (a.atol + rabs(Y) * a.rtol) : R(1);
                 const R q0 = Y / sc, q1 = K1 / sc;
+                if constexpr (sizeof(R) == 4) {
                 const float dn0 = sqrtf((float)first_lane(oct_allsum(q0 * q0)) / 6.0f);
                 const float dn1 = sqrtf((float)first_lane(oct_allsum(q1 * q1)) / 6.0f);
                 float h0 = (dn0 < 1e-5f || dn1 < 1e-5f) ? 1e-6f : 0.01f * dn0 / dn1;
@@ -311,6 +316,17 @@ __device__ __forceinline__ void solve_one(const SolveArgs<R> &a, const int b, co
                 const float h1 = (dn1 <= 1e-15f && dn2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f)
                                                                    : powf(0.01f / fmaxf(dn1, dn2), 0.2f);
                 h_abs = first_lane((R)fminf(fminf(100.0f * h0, h1), (float)len));
+                } else {
+                const double dn0 = sqrt((double)first_lane(oct_allsum(q0 * q0)) / 6.0);
+                const double dn1 = sqrt((double)first_lane(oct_allsum(q1 * q1)) / 6.0);
+                double h0 = (dn0 < 1e-5 || dn1 < 1e-5) ? 1e-6 : 0.01 * dn0 / dn1;
+                h0 = fmin(h0, (double)len);
+                const R f1 = f_at(t0 + (R)h0, rfma((R)h0, K1, Y), nullptr);
+                const R q2 = (f1 - K1) / sc;
+                const double dn2 = sqrt((double)first_lane(oct_allsum(q2 * q2)) / 6.0) / h0;
+                const double h1 = (dn1 <= 1e-15 && dn2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(dn1, dn2), 0.2);
+                h_abs = first_lane((R)fmin(fmin(100.0 * h0, h1), (double)len));
+                }
                 if constexpr (kUnrolled) KF = K1;
                 else KK = (grp == 0) ? K1 : R(0);
                 nf += 2;
@@ -378,12 +394,13 @@ __device__ __forceinline__ void solve_one(const SolveArgs<R> &a, const int b, co
                     R qall = rdiv(err, a.atol + ymax * a.rtol);
                     asm volatile("" : "+v"(qall));
                     const R qe = (c8 < 6) ? qall : R(0);
-                    float en = first_lane(rms6<R>((float)first_lane(oct_allsum(qe * qe))));   // scalar from here on
+                    using CT = CtlT<R>;
+                    CT en = first_lane(rms6<R>((CT)first_lane(oct_allsum(qe * qe))));   // scalar from here on
                     const float ysum = (float)first_lane(oct_allsum(Yn));
-                    if (!(en == en) || !(fabsf(ysum) <= 3.0e38f) || !(fabsf(en) <= 3.0e38f)) en = 1e30f;
-                    if (en < 1.0f) {
-                        float fac = (en == 0.0f) ? 10.0f : fminf(10.0f, 0.9f * pow_m02<R>(en));
-                        if (rejected) fac = fminf(1.0f, fac);
+                    if (!(en == en) || !(fabsf(ysum) <= 3.0e38f) || !(fabsf((float)en) <= 3.0e38f)) en = CT(1e30f);
+                    if (en < CT(1)) {
+                        CT fac = (en == CT(0)) ? CT(10) : (CT)fmin(CT(10), CT(0.9) * pow_m02<R>(en));
+                        if (rejected) fac = (CT)fmin(CT(1), fac);
                         tape_put(tc, h, clipped);
                         const R hn = first_lane(h * (R)fac);
                         h_abs = (clipped && hn < h_abs) ? h_abs : hn;               // a clipped step never shrinks the proposal
@@ -394,9 +411,9 @@ __device__ __forceinline__ void solve_one(const SolveArgs<R> &a, const int b, co
                         ns++;
                         break;
                     } else {
-                        h_abs = first_lane(h * (R)fmaxf(0.2f, 0.9f * pow_m02<R>(en)));
+                        h_abs = first_lane(h * (R)fmax(CT(0.2), CT(0.9) * pow_m02<R>(en)));
                         rejected = true;
-                        if (en >= 1e30f && !(h_abs > min_step)) { st = HODE_ST_NONFINITE; break; }
+                        if (en >= CT(1e30f) && !(h_abs > min_step)) { st = HODE_ST_NONFINITE; break; }
                     }
                 }
             }

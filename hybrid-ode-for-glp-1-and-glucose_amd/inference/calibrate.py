@@ -53,7 +53,7 @@ def levenberg_marquardt(fn: Callable, z0: torch.Tensor, prior_w: torch.Tensor, m
     eye = torch.eye(K, dtype=dt, device=dev)
 
     def objective(r, zz):
-        return 0.5 * (r * r).sum(1) + 0.5 * (pw * zz * zz).sum(1)
+        return 0.5 * _tree_sum(r * r) + 0.5 * _tree_sum(pw * zz * zz)
 
     for it in range(max_iter + 1):
         r, J, ok = fn(z, True)
@@ -63,9 +63,9 @@ def levenberg_marquardt(fn: Callable, z0: torch.Tensor, prior_w: torch.Tensor, m
         J = torch.where(ok.reshape(B, 1, 1), J, torch.zeros((), dtype=dt, device=dev))
         r = torch.where(ok.reshape(B, 1), r, torch.zeros((), dtype=dt, device=dev))
         F = objective(r, z)
-        JtJ = J.transpose(1, 2) @ J
+        JtJ = _tree_sum(J.unsqueeze(3) * J.unsqueeze(2))
         A = JtJ + torch.diag_embed(pw.expand(B, K))
-        g = (J.transpose(1, 2) @ r.unsqueeze(2)).squeeze(2) + pw * z
+        g = _tree_sum(J * r.unsqueeze(2)) + pw * z
         gn = g.abs().amax(1)
         if g0 is None:
             g0 = gn.clone()
@@ -76,7 +76,8 @@ def levenberg_marquardt(fn: Callable, z0: torch.Tensor, prior_w: torch.Tensor, m
         ok_a = torch.isfinite(A).flatten(1).all(1)
         A_gn = torch.where(ok_a.reshape(B, 1, 1), A + 1e-14 * torch.diag_embed(dg), eye)
         step_gn = torch.linalg.solve(A_gn, torch.where(ok_a.reshape(B, 1), g, torch.zeros((), dtype=dt, device=dev)))
-        near = ok_a & (step_gn.norm(dim=1) <= xtol * (xtol + z.norm(dim=1)))
+        norm = lambda v: _tree_sum(v * v).sqrt()            # noqa: E731
+        near = ok_a & (norm(step_gn) <= xtol * (xtol + norm(z)))
         conv = ~done & ((gn <= gtol * g0.clamp_min(tiny)) | near)
         status[conv] = ST_CONVERGED
         done |= conv
@@ -93,7 +94,7 @@ def levenberg_marquardt(fn: Callable, z0: torch.Tensor, prior_w: torch.Tensor, m
         n_iter += moving.to(torch.int32)
         z = torch.where(acc.reshape(B, 1), z_try, z)
         # gain ratio: actual over predicted decrease of the quadratic model, -g.delta - 1/2 delta.A.delta
-        pred = -(g * delta).sum(1) - 0.5 * (delta.unsqueeze(1) @ A @ delta.unsqueeze(2)).reshape(B)
+        pred = -_tree_sum(g * delta) - 0.5 * _tree_sum(delta * _tree_sum((A * delta.unsqueeze(1)).transpose(1, 2)))
         rho = (F - F_t) / pred.clamp_min(tiny)
         shrink = torch.clamp(1.0 - (2.0 * rho - 1.0) ** 3, min=1.0 / 3.0)
         lam = torch.where(acc, (lam * shrink).clamp_min(1e-12), torch.where(moving, lam * nu, lam))
@@ -101,9 +102,20 @@ def levenberg_marquardt(fn: Callable, z0: torch.Tensor, prior_w: torch.Tensor, m
         # no damping makes progress any more: stop.  Converged when the Gauss-Newton step is below the resolution of F itself
         # (a decrease of 1/2 step.A.step under one rounding of F cannot be seen), status 1 otherwise
         stuck = moving & ~acc & (lam > 1e16)
-        status[stuck & ok_a & (step_gn.norm(dim=1) <= 1e-7 * (1.0 + z.norm(dim=1)))] = ST_CONVERGED
+        status[stuck & ok_a & (norm(step_gn) <= 1e-7 * (1.0 + norm(z)))] = ST_CONVERGED
         done |= stuck
     return dict(z=z, F=F, A=A, JtJ=JtJ, status=status, n_iter=n_iter)
+
+
+def _tree_sum(x):
+    """Sum over dim 1 in a fixed pairwise order made of elementwise additions: a patient's bits do not depend on who else is in the
+    batch (a batched GEMM or a library reduction may pick its summation order by the batch size, and fifty LM steps of an
+    ill-conditioned patient carry that last bit into the eighth digit of the fit)."""
+    while x.shape[1] > 1:
+        h = x.shape[1] // 2
+        y = x[:, :h] + x[:, h:2 * h]
+        x = torch.cat([y, x[:, 2 * h:]], 1) if x.shape[1] > 2 * h else y
+    return x[:, 0]
 
 
 def _finite_rows(A):

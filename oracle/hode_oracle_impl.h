@@ -128,10 +128,13 @@ static void SFX(rhs_one)(const SFX(mlp_t) *m, const REAL *ode, REAL t, const REA
     f[5] = dFFA + out6[5];
 }
 
-/* VJP of rhs_one: given lam (6) returns gx (6) += J^T lam, accumulates gnn, gode (may be NULL). */
+/* VJP of rhs_one: given lam (6) returns gx (6) += J^T lam, accumulates gnn, gode (may be NULL).
+ * gin (may be NULL) receives the cotangents of the external inputs of this evaluation: gin[0] meal (enters dG additively),
+ * gin[1] tVNS (input 8 of the first layer), gin[2] GD (through the Hill term of k_GE; 0 at GD <= 0, the convention of the
+ * IGD_50 / g gradients below). */
 static void SFX(rhs_vjp_one)(const SFX(mlp_t) *m, const REAL *ode, REAL t, const REAL *x,
                              REAL meal, REAL tvns, REAL gd, int use_gd, const REAL *lam,
-                             REAL *gx, ACC *gnn, ACC *gode, REAL scale)
+                             REAL *gx, ACC *gnn, ACC *gode, REAL scale, REAL *gin)
 {
     REAL act[HODE_MAXL + 1][HODE_MAXH];
     REAL f[6];
@@ -199,6 +202,12 @@ static void SFX(rhs_vjp_one)(const SFX(mlp_t) *m, const REAL *ode, REAL t, const
     for (int i = 0; i < 6; ++i) o[i] += prev[1 + i];
     o[3] += prev[7];
     for (int i = 0; i < 6; ++i) gx[i] += o[i];
+    if (gin) {
+        gin[0] = lam[0];
+        gin[1] = prev[8];
+        gin[2] = 0;
+        if (use_gd && gd > 0) gin[2] = lam[0] * k_GE0 * G * g * u * v / (gd * (v + u) * (v + u));
+    }
 }
 
 /* ---- batched RHS entry points -------------------------------------------------------------- */
@@ -214,9 +223,11 @@ int SFX(hode_oracle_rhs)(int B, const REAL *x, const REAL *t, const REAL *meal, 
     return 0;
 }
 
-int SFX(hode_oracle_rhs_vjp)(int B, const REAL *x, const REAL *t, const REAL *meal, const REAL *tvns,
-                             const REAL *gd, const REAL *ode, const REAL *nn_p, int H, int L,
-                             const REAL *gout, REAL *gx, REAL *gnn, REAL *gode)
+/* gmeal / gtvns / ggd [B] (each may be NULL): the cotangents of the inputs, per sample */
+int SFX(hode_oracle_rhs_vjp_inputs)(int B, const REAL *x, const REAL *t, const REAL *meal, const REAL *tvns,
+                                    const REAL *gd, const REAL *ode, const REAL *nn_p, int H, int L,
+                                    const REAL *gout, REAL *gx, REAL *gnn, REAL *gode, REAL *gmeal, REAL *gtvns,
+                                    REAL *ggd)
 {
     SFX(mlp_t) m;
     int P = SFX(mlp_bind)(&m, nn_p, H, L);
@@ -224,16 +235,26 @@ int SFX(hode_oracle_rhs_vjp)(int B, const REAL *x, const REAL *t, const REAL *me
     ACC *an = (ACC *)calloc((size_t)P, sizeof(ACC));
     ACC ao[17] = {0};
     for (int b = 0; b < B; ++b) {
-        REAL g6[6] = {0, 0, 0, 0, 0, 0};
+        REAL g6[6] = {0, 0, 0, 0, 0, 0}, gi[3];
         SFX(rhs_vjp_one)(&m, ode, t ? t[b] : 0, x + 6 * b, meal ? meal[b] : 0, tvns ? tvns[b] : 0,
                          gd ? gd[b] : 0, gd != NULL, gout + 6 * b, g6, gnn ? an : NULL,
-                         gode ? ao : NULL, (REAL)1);
+                         gode ? ao : NULL, (REAL)1, gi);
         for (int i = 0; i < 6; ++i) gx[6 * b + i] = g6[i];
+        if (gmeal) gmeal[b] = gi[0];
+        if (gtvns) gtvns[b] = gi[1];
+        if (ggd) ggd[b] = gi[2];
     }
     if (gnn) for (int i = 0; i < P; ++i) gnn[i] = (REAL)an[i];
     if (gode) for (int i = 0; i < 17; ++i) gode[i] = (REAL)ao[i];
     free(an);
     return 0;
+}
+
+int SFX(hode_oracle_rhs_vjp)(int B, const REAL *x, const REAL *t, const REAL *meal, const REAL *tvns,
+                             const REAL *gd, const REAL *ode, const REAL *nn_p, int H, int L,
+                             const REAL *gout, REAL *gx, REAL *gnn, REAL *gode)
+{
+    return SFX(hode_oracle_rhs_vjp_inputs)(B, x, t, meal, tvns, gd, ode, nn_p, H, L, gout, gx, gnn, gode, NULL, NULL, NULL);
 }
 
 /* ---- forcing on one grid interval (hybrid_ode_nn.py:217-231) ------------------------------- */
@@ -452,13 +473,20 @@ int SFX(hode_oracle_solve)(int B, int T, const REAL *x0, const REAL *tg, int t_b
  * steps recorded on the tape (step sizes treated as constants).  Gradient accumulators are ACC.
  *   gy[B,T,6] = dLoss/dy  ->  gx0[B,6], gnn[P], gode[17]
  * No reference counterpart exists; checked against finite differences in tests.
+ *   gmeal / gtvns / ggd (each may be NULL; ignored for an input of mode 0): dLoss/d(input), shaped like the input -- [B] in
+ *   mode 1, [B,T] in mode 2.  The CALLER zeroes them: a stage on interval k with lerp weight al adds (1 - al) c to row k and
+ *   al c to row k + 1, so a row that bounds no taped step (inside a run of repeated times, after a failure) stays 0.
+ *   Pinned to reference autograd (fixture G10) by tests/test_input_grads_oracle.py.
  */
-int SFX(hode_oracle_solve_bwd)(int B, int T, const REAL *tg, int t_batched, const REAL *meal,
-                               int meal_mode, const REAL *tvns, int tvns_mode, const REAL *gd,
-                               int gd_mode, const REAL *ode, const REAL *nn_p, int H, int L,
-                               int method, int max_steps, const int *nsteps, const int *status, const void *tape_v,
-                               const REAL *gy, REAL *gx0, REAL *gnn, REAL *gode)
+int SFX(hode_oracle_solve_bwd_inputs)(int B, int T, const REAL *tg, int t_batched, const REAL *meal,
+                                      int meal_mode, const REAL *tvns, int tvns_mode, const REAL *gd,
+                                      int gd_mode, const REAL *ode, const REAL *nn_p, int H, int L,
+                                      int method, int max_steps, const int *nsteps, const int *status, const void *tape_v,
+                                      const REAL *gy, REAL *gx0, REAL *gnn, REAL *gode, REAL *gmeal, REAL *gtvns, REAL *ggd)
 {
+    REAL *gq[3] = {gmeal, gtvns, ggd};
+    const int mq[3] = {meal_mode, tvns_mode, gd_mode};
+    const int want_gin = (gmeal && meal_mode) || (gtvns && tvns_mode) || (ggd && gd_mode);
     SFX(mlp_t) m;
     int P = SFX(mlp_bind)(&m, nn_p, H, L);
     if (P < 0) return -1;
@@ -534,8 +562,20 @@ int SFX(hode_oracle_solve_bwd)(int B, int T, const REAL *tg, int t_batched, cons
                 }
                 for (int i = 0; i < 6; ++i) Ybar[sI][i] = 0;
                 SFX(seg_eval)(&s, ts[sI], &mm, &vv, &dd);
+                REAL gi[3];
                 SFX(rhs_vjp_one)(&m, ode, ts[sI], Y[sI], mm, vv, dd, s.use_gd, kb, Ybar[sI],
-                                 gnn ? an : NULL, gode ? ao : NULL, (REAL)1);
+                                 gnn ? an : NULL, gode ? ao : NULL, (REAL)1, want_gin ? gi : NULL);
+                if (want_gin) {
+                    const REAL al = (ts[sI] - s.t0) / (s.t1 - s.t0);     /* as seg_eval forms it */
+                    for (int q = 0; q < 3; ++q) {
+                        if (!gq[q] || mq[q] == 0) continue;
+                        if (mq[q] == 1) gq[q][b] += gi[q];
+                        else {
+                            gq[q][(size_t)b * T + k] += ((REAL)1 - al) * gi[q];
+                            gq[q][(size_t)b * T + k + 1] += al * gi[q];
+                        }
+                    }
+                }
                 for (int i = 0; i < 6; ++i) newlam[i] += Ybar[sI][i];
             }
             for (int i = 0; i < 6; ++i) lam[i] = newlam[i];
@@ -552,4 +592,14 @@ int SFX(hode_oracle_solve_bwd)(int B, int T, const REAL *tg, int t_batched, cons
     if (gode) for (int i = 0; i < 17; ++i) gode[i] = (REAL)ao[i];
     free(an);
     return 0;
+}
+
+int SFX(hode_oracle_solve_bwd)(int B, int T, const REAL *tg, int t_batched, const REAL *meal,
+                               int meal_mode, const REAL *tvns, int tvns_mode, const REAL *gd,
+                               int gd_mode, const REAL *ode, const REAL *nn_p, int H, int L,
+                               int method, int max_steps, const int *nsteps, const int *status, const void *tape_v,
+                               const REAL *gy, REAL *gx0, REAL *gnn, REAL *gode)
+{
+    return SFX(hode_oracle_solve_bwd_inputs)(B, T, tg, t_batched, meal, meal_mode, tvns, tvns_mode, gd, gd_mode, ode, nn_p, H, L,
+                                             method, max_steps, nsteps, status, tape_v, gy, gx0, gnn, gode, NULL, NULL, NULL);
 }

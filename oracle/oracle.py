@@ -107,6 +107,28 @@ def rhs_vjp(x, t, meal, tvns, gd, ode, nn_p, H, L, gout, dtype=np.float32):
     return gx, gnn, gode
 
 
+INPUT_KEYS = ("meal", "tVNS", "GD")
+
+
+def rhs_vjp_inputs(x, t, meal, tvns, gd, ode, nn_p, H, L, gout, dtype=np.float32, want_inputs=INPUT_KEYS):
+    """rhs_vjp() + the cotangents of the external inputs: returns (gx, gnn, gode, {"meal", "tVNS", "GD"}), an entry [B] for an
+    input that is given and wanted, else None.  GD <= 0 has gradient 0 (the convention of the IGD_50 / g gradients)."""
+    x = _arr(x, dtype)
+    B = x.shape[0]
+    t, meal, tvns, gd, gout = (_arr(v, dtype) for v in (t, meal, tvns, gd, gout))
+    ode, nn_p = _arr(ode, dtype), _arr(nn_p, dtype)
+    gx = np.zeros((B, 6), dtype)
+    gnn = np.zeros(nn_p.size, dtype)
+    gode = np.zeros(17, dtype)
+    gin = {k: (np.zeros(B, dtype) if (u is not None and k in want_inputs) else None)
+           for k, u in zip(INPUT_KEYS, (meal, tvns, gd))}
+    rc = getattr(lib(), f"hode_oracle_rhs_vjp_inputs_{_sfx(dtype)}")(
+        C.c_int(B), _p(x), _p(t), _p(meal), _p(tvns), _p(gd), _p(ode), _p(nn_p), C.c_int(H), C.c_int(L),
+        _p(gout), _p(gx), _p(gnn), _p(gode), *(_p(gin[k]) for k in INPUT_KEYS))
+    assert rc == 0
+    return gx, gnn, gode, gin
+
+
 class Solution:
     __slots__ = ("y", "status", "nsteps", "nfev", "tape", "max_steps", "args")
 
@@ -160,6 +182,29 @@ def solve_bwd(sol, gy, want_gnn=True, want_gode=True):
         C.c_int(sol.max_steps), _p(sol.nsteps), _p(sol.status), _p(sol.tape), _p(gy), _p(gx0), _p(gnn), _p(gode))
     assert rc == 0
     return gx0, gnn, gode
+
+
+def solve_bwd_inputs(sol, gy, want_gnn=True, want_gode=True, want_inputs=INPUT_KEYS):
+    """solve_bwd() + the gradients of the external inputs: returns (gx0, gnn, gode, {"meal", "tVNS", "GD"}), an entry shaped like
+    the input ([B] constant, [B,T] on the grid; rows that bound no taped step are 0), None for an absent or unwanted input."""
+    t, t_batched, meal, tvns, gd, ode, nn_p, H, L, method, dtype = sol.args
+    assert sol.tape is not None
+    B, T = sol.y.shape[:2]
+    gy = _arr(gy, dtype)
+    assert gy.shape == (B, T, 6)
+    gx0 = np.zeros((B, 6), dtype)
+    gnn = np.zeros(nn_p.size, dtype) if want_gnn else None
+    gode = np.zeros(17, dtype) if want_gode else None
+    gin = {k: (np.zeros(u.shape, dtype) if (u is not None and k in want_inputs) else None)
+           for k, u in zip(INPUT_KEYS, (meal, tvns, gd))}
+    rc = getattr(lib(), f"hode_oracle_solve_bwd_inputs_{_sfx(dtype)}")(
+        C.c_int(B), C.c_int(T), _p(t), C.c_int(t_batched),
+        _p(meal), C.c_int(_mode(meal, B, T)), _p(tvns), C.c_int(_mode(tvns, B, T)),
+        _p(gd), C.c_int(_mode(gd, B, T)), _p(ode), _p(nn_p), C.c_int(H), C.c_int(L), C.c_int(method),
+        C.c_int(sol.max_steps), _p(sol.nsteps), _p(sol.status), _p(sol.tape), _p(gy), _p(gx0), _p(gnn), _p(gode),
+        *(_p(gin[k]) for k in INPUT_KEYS))
+    assert rc == 0
+    return gx0, gnn, gode, gin
 
 
 def solve_reference_mode(x0, t, meal, tvns, gd, ode, nn_p, H, L, rtol=1e-6, atol=1e-8):
