@@ -15,6 +15,14 @@
 //               lane 12 consecutive entries (two rows of six states), so the state of every accumulator is a compile-time
 //               index, as in hode_obs.hip; a call whose length (N % 4 != 0) or pointers rule the wide accesses out goes row
 //               by row, six scalars per lane, the state again a compile-time index.
+//   pred_tails  folds the draws into the K smallest and the K largest values of every entry (two binary heaps per entry in
+//               global memory, slot-major so a wave's accesses at one depth coalesce): a lane owns one entry as in pred_fold,
+//               keeps the count and the two heap roots in registers, and only a value that passes a root -- about
+//               K (1 + ln(S / K)) of S draws per tail -- walks a heap, O(log K) loads and stores.  A draw is a pure update of
+//               the state in memory, so any split of the draws gives the same bits and any order the same multisets.
+//   pred_quantiles  sorts the two buffers in place (heapsort, then reversed: a sorted buffer is still a heap, so folding may
+//               go on) and interpolates every level between two order statistics in fp64 (numpy's "linear" method); the band
+//               table [6][4] of the outer pair of levels against the data is reduced as the score table is.
 // There are no floating-point atomics in this file: the same call gives the same bits.
 #include "hode_chains.h"
 
@@ -376,6 +384,260 @@ int pred_score(void *stream, int64_t N, const int32_t *n, const double *mean, co
     return done();
 }
 
+// ------------------------------------------------------------------------------------------------------------ tails
+// The K smallest and the K largest values of every entry across the draws: what an empirical tail quantile needs of them.
+// lo[K][N] is a binary max-heap of the smallest values taken (its root, slot 0, the largest of them: the threshold a new value
+// must be below to enter), hi[K][N] a min-heap of the largest; slot j of entry i is at j * N + i, so the lanes of a wave touch
+// consecutive addresses at the same depth.  Values are copied and compared with <, never computed with.
+template <typename R> struct TailArgs {
+    int n_draws;
+    int64_t N, row_len, n_traj, K;
+    const R *y;
+    const int32_t *status;
+    int32_t *cnt;
+    R *lo, *hi;
+};
+
+// heap order: in a max-heap a parent is not below its children, in a min-heap not above.  `max` is a run-time value so that
+// the lanes of a wave that walk lo and the lanes that walk hi share one loop
+template <typename R> __device__ __forceinline__ bool below(bool max, R a, R b) { return max ? a < b : b < a; }
+
+// v into the hole at slot p of entry i's heap, the hole rising while its parent is below v
+template <typename R> __device__ __forceinline__ void sift_up(R *h, bool max, int64_t N, int64_t i, int64_t p, R v)
+{
+    while (p > 0) {
+        const int64_t q = (p - 1) >> 1;
+        const R u = h[q * N + i];
+        if (!below(max, u, v)) break;
+        h[p * N + i] = u;
+        p = q;
+    }
+    h[p * N + i] = v;
+}
+
+// v into the hole at the root of entry i's heap of `size` slots, the hole sinking while v is below its greater child;
+// returns the new root
+template <typename R> __device__ __forceinline__ R sift_down(R *h, bool max, int64_t N, int64_t i, int64_t size, R v)
+{
+    int64_t p = 0;
+    R root = v;
+    for (;;) {
+        int64_t c = 2 * p + 1;
+        if (c >= size) break;
+        R u = h[c * N + i];
+        if (c + 1 < size) {
+            const R w = h[(c + 1) * N + i];
+            if (below(max, u, w)) { u = w; c += 1; }
+        }
+        if (!below(max, v, u)) break;
+        h[p * N + i] = u;
+        if (p == 0) root = u;
+        p = c;
+    }
+    h[p * N + i] = v;
+    return root;
+}
+
+// One lane, one entry, all draws of the call, as pred_fold_kernel.  cnt and the two roots stay in registers; a draw that
+// passes neither root (all but about K (1 + ln(S / K)) of S draws per tail) costs its load and two compares.
+template <typename R> __global__ __launch_bounds__(kThreads) void pred_tails_kernel(const TailArgs<R> a)
+{
+    constexpr int kFly = 16;                           // draws whose loads are in flight together
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= a.N) return;
+    const int64_t tr = i / a.row_len;
+    int32_t cnt = a.cnt[i];
+    R top_lo = cnt > 0 ? a.lo[i] : R(0), top_hi = cnt > 0 ? a.hi[i] : R(0);
+
+    auto take = [&](R v, int32_t st) {
+        if (st != 0 || !__builtin_isfinite(v)) return;
+        const bool filling = cnt < a.K;                                        // both buffers still take everything
+        unsigned need = filling ? 3u : ((v < top_lo ? 1u : 0u) | (top_hi < v ? 2u : 0u));          // bit 0: into lo, bit 1: into hi
+        while (need) {                                 // ONE loop for both buffers: a lane in lo and a lane in hi walk together
+            const bool max = need & 1u;
+            R *h = max ? a.lo : a.hi;
+            const R top = max ? top_lo : top_hi;
+            R root;
+            if (filling) {
+                sift_up(h, max, a.N, i, cnt, v);
+                root = (cnt == 0 || below(max, top, v)) ? v : top;
+            } else {
+                root = sift_down(h, max, a.N, i, a.K, v);
+            }
+            if (max) top_lo = root;
+            else top_hi = root;
+            need &= max ? 2u : 0u;
+        }
+        cnt += 1;
+    };
+
+    int s = 0;
+    for (; s + kFly <= a.n_draws; s += kFly) {
+        R yv[kFly];
+        int32_t st[kFly];
+#pragma unroll
+        for (int f = 0; f < kFly; ++f) {
+            yv[f] = a.y[(int64_t)(s + f) * a.N + i];
+            st[f] = a.status ? a.status[(int64_t)(s + f) * a.n_traj + tr] : 0;
+        }
+#pragma unroll
+        for (int f = 0; f < kFly; ++f) take(yv[f], st[f]);
+    }
+    for (; s < a.n_draws; ++s) take(a.y[(int64_t)s * a.N + i], a.status ? a.status[(int64_t)s * a.n_traj + tr] : 0);
+    a.cnt[i] = cnt;
+}
+
+template <typename R>
+int pred_tails(void *stream, int n_draws, int64_t N, const R *y, const int32_t *status, int64_t row_len, int64_t K, int32_t *cnt, R *lo,
+               R *hi)
+{
+    if (n_draws < 0 || N < 1 || K < 1 || !cnt || !lo || !hi) return HODE_EINVAL;
+    if (n_draws > 0 && !y) return HODE_EINVAL;
+    if (status && (row_len < 1 || N % row_len)) return HODE_EINVAL;
+    if ((n_draws > 0 && N > (((int64_t)1 << 62) / n_draws)) || N > (((int64_t)1 << 62) / K)) return HODE_EINVAL;   // inside int64
+    if (n_draws == 0) return HODE_OK;
+    TailArgs<R> a{};
+    a.n_draws = n_draws; a.N = N; a.row_len = status ? row_len : N; a.n_traj = N / a.row_len; a.K = K;
+    a.y = y; a.status = status; a.cnt = cnt; a.lo = lo; a.hi = hi;
+    const int64_t blocks = (N + kThreads - 1) / kThreads;
+    if (blocks > 0x7fffffff) return HODE_EUNSUPPORTED;
+    hipLaunchKernelGGL((pred_tails_kernel<R>), dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, a);
+    return done();
+}
+
+// -------------------------------------------------------------------------------------------------------- quantiles
+template <typename R> struct QuantArgs {
+    int64_t N, K;
+    const int32_t *cnt;
+    R *lo, *hi;
+    int n_levels;
+    double levels[HODE_PRED_MAX_LEVELS];
+    R *out;
+};
+
+// entry i's heap of m slots sorted in place, greatest first for a max-heap and least first for a min-heap (so it is still a
+// heap): heapsort leaves the opposite order, which is then reversed
+template <typename R> __device__ __forceinline__ void sort_heap(R *h, bool max, int64_t N, int64_t i, int64_t m)
+{
+    for (int64_t end = m - 1; end > 0; --end) {
+        const R v = h[end * N + i];
+        h[end * N + i] = h[i];
+        sift_down(h, max, N, i, end, v);
+    }
+    for (int64_t l = 0, r = m - 1; l < r; ++l, --r) {
+        const R u = h[l * N + i], w = h[r * N + i];
+        h[l * N + i] = w;
+        h[r * N + i] = u;
+    }
+}
+
+// One lane, one entry: sort both buffers, then numpy's "linear" quantile of every level from the nearer one.
+template <typename R> __global__ __launch_bounds__(kThreads) void pred_quantiles_kernel(const QuantArgs<R> a)
+{
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= a.N) return;
+    const int64_t n = a.cnt[i], m = n < a.K ? n : a.K;
+    sort_heap(a.lo, true, a.N, i, m);
+    sort_heap(a.hi, false, a.N, i, m);
+    for (int l = 0; l < a.n_levels; ++l) {
+        const double q = a.levels[l];
+        double r = __builtin_nan("");
+        if (n > 0) {
+            const double h = q * (double)(n - 1), fj = floor(h), g = h - fj;
+            const int64_t j = (int64_t)fj, jb = j + 1 < n - 1 ? j + 1 : n - 1;
+            if (q <= 0.5) {                            // rank r (ascending) is slot m - 1 - r of lo
+                if (jb < m) {
+                    const double va = (double)a.lo[(m - 1 - j) * a.N + i], vb = (double)a.lo[(m - 1 - jb) * a.N + i];
+                    r = va + (vb - va) * g;
+                }
+            } else {                                   // rank r is slot r - (n - m) of hi
+                if (j >= n - m) {
+                    const double va = (double)a.hi[(j - (n - m)) * a.N + i], vb = (double)a.hi[(jb - (n - m)) * a.N + i];
+                    r = va + (vb - va) * g;
+                }
+            }
+        }
+        a.out[(int64_t)l * a.N + i] = (R)r;
+    }
+}
+
+template <typename R> struct BandArgs {
+    int64_t N;
+    const int32_t *cnt;
+    const R *qlo, *qhi, *obs;
+    const uint8_t *mask;
+    double two_over_alpha;
+    double *work;
+};
+
+// per-state sums of the band [qlo, qhi] against the observations, a lane taking rows of six entries (the state a compile-time
+// index), reduced as pred_score_kernel reduces: work[block][6][4]
+template <typename R> __global__ __launch_bounds__(kThreads) void pred_band_kernel(const BandArgs<R> a)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[24];
+    double s[6][2];
+    int c[6][2];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s[k][0] = s[k][1] = 0.0, c[k][0] = c[k][1] = 0;
+    for (int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x; g < a.N / 6; g += (int64_t)gridDim.x * kThreads) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const int64_t i = 6 * g + k;
+            const R ob = a.obs[i];
+            if (!seen(ob, a.mask ? (unsigned)a.mask[i] : 1u) || a.cnt[i] < 2) continue;
+            const double lo = (double)a.qlo[i], hi = (double)a.qhi[i], o = (double)ob;
+            if (!__builtin_isfinite(lo) || !__builtin_isfinite(hi)) continue;
+            c[k][0] += 1;
+            s[k][0] += hi - lo;
+            c[k][1] += (lo <= o && o <= hi) ? 1 : 0;
+            s[k][1] += (hi - lo) + a.two_over_alpha * ((o < lo ? lo - o : 0.0) + (o > hi ? o - hi : 0.0));
+        }
+    }
+    double *row = a.work + (int64_t)blockIdx.x * 6 * HODE_PRED_BAND_COLS;
+#pragma unroll
+    for (int col = 0; col < HODE_PRED_BAND_COLS; ++col) {
+        double v[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v[k] = (col & 1) ? s[k][col >> 1] : (double)c[k][col >> 1];
+        block_sum6(v, sh);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) row[k * HODE_PRED_BAND_COLS + col] = v[k];
+        }
+    }
+}
+
+template <typename R>
+int pred_quantiles(void *stream, int64_t N, int64_t K, const int32_t *cnt, R *lo, R *hi, int n_levels, const double *levels, R *out,
+                   const R *obs, const uint8_t *mask, double *band_table, double *work)
+{
+    if (N < 1 || K < 1 || !cnt || !lo || !hi || !levels || !out || n_levels < 1 || n_levels > HODE_PRED_MAX_LEVELS) return HODE_EINVAL;
+    if (N > (((int64_t)1 << 62) / K) || N > (((int64_t)1 << 62) / n_levels)) return HODE_EINVAL;
+    for (int l = 0; l < n_levels; ++l)
+        if (!(levels[l] > 0.0 && levels[l] < 1.0) || (l > 0 && !(levels[l - 1] < levels[l]))) return HODE_EINVAL;
+    if (mask && !obs) return HODE_EINVAL;
+    if (band_table && (N % 6 || !obs || !work || n_levels < 2 || !(levels[0] < 0.5 && 0.5 < levels[n_levels - 1]))) return HODE_EINVAL;
+    QuantArgs<R> a{};
+    a.N = N; a.K = K; a.cnt = cnt; a.lo = lo; a.hi = hi; a.n_levels = n_levels; a.out = out;
+    for (int l = 0; l < n_levels; ++l) a.levels[l] = levels[l];
+    const int64_t blocks = (N + kThreads - 1) / kThreads;
+    if (blocks > 0x7fffffff) return HODE_EUNSUPPORTED;
+    hipLaunchKernelGGL((pred_quantiles_kernel<R>), dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, a);
+    if (band_table) {
+        BandArgs<R> b{};
+        b.N = N; b.cnt = cnt; b.qlo = out; b.qhi = out + (int64_t)(n_levels - 1) * N; b.obs = obs; b.mask = mask; b.work = work;
+        b.two_over_alpha = 2.0 / (1.0 - (levels[n_levels - 1] - levels[0]));
+        const int64_t want = (N / 6 + kThreads - 1) / kThreads;
+        const int nb = (int)(want < kScoreBlocks ? want : kScoreBlocks);
+        hipLaunchKernelGGL((pred_band_kernel<R>), dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, b);
+        hipLaunchKernelGGL(pred_score_finish_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, nb, 6 * HODE_PRED_BAND_COLS, work,
+                           band_table);
+    }
+    return done();
+}
+
 }  // namespace
 }  // namespace hode
 
@@ -406,6 +668,26 @@ int hode_pred_score_f64(void *stream, int64_t N, const int32_t *n, const double 
 {
     return hode::pred_score<double>(stream, N, n, mean, m2, pit, lmax, lsum, obs, mask, extra_var, thr, n_bins, out_mean, out_sd, out_pit,
                                     table, work);
+}
+int hode_pred_tails_f32(void *stream, int n_draws, int64_t N, const float *y, const int32_t *status, int64_t row_len, int K, int32_t *cnt,
+                        float *lo, float *hi)
+{
+    return hode::pred_tails<float>(stream, n_draws, N, y, status, row_len, K, cnt, lo, hi);
+}
+int hode_pred_tails_f64(void *stream, int n_draws, int64_t N, const double *y, const int32_t *status, int64_t row_len, int K, int32_t *cnt,
+                        double *lo, double *hi)
+{
+    return hode::pred_tails<double>(stream, n_draws, N, y, status, row_len, K, cnt, lo, hi);
+}
+int hode_pred_quantiles_f32(void *stream, int64_t N, int K, const int32_t *cnt, float *lo, float *hi, int n_levels, const double *levels,
+                            float *out, const float *obs, const uint8_t *mask, double *band_table, double *work)
+{
+    return hode::pred_quantiles<float>(stream, N, K, cnt, lo, hi, n_levels, levels, out, obs, mask, band_table, work);
+}
+int hode_pred_quantiles_f64(void *stream, int64_t N, int K, const int32_t *cnt, double *lo, double *hi, int n_levels, const double *levels,
+                            double *out, const double *obs, const uint8_t *mask, double *band_table, double *work)
+{
+    return hode::pred_quantiles<double>(stream, N, K, cnt, lo, hi, n_levels, levels, out, obs, mask, band_table, work);
 }
 
 }  // extern "C"

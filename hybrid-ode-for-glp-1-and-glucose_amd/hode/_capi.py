@@ -29,7 +29,8 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_nuts_begin_f32", "hode_nuts_begin_f64", "hode_nuts_pre_f32", "hode_nuts_pre_f64", "hode_nuts_post_f32",
            "hode_nuts_post_f64", "hode_nuts_compact", "hode_nuts_finish_f32", "hode_nuts_finish_f64",
            "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64", "hode_sobol_indices_f32", "hode_sobol_indices_f64",
-           "hode_pred_fold_f32", "hode_pred_fold_f64", "hode_pred_score_f32", "hode_pred_score_f64"]
+           "hode_pred_fold_f32", "hode_pred_fold_f64", "hode_pred_score_f32", "hode_pred_score_f64",
+           "hode_pred_tails_f32", "hode_pred_tails_f64", "hode_pred_quantiles_f32", "hode_pred_quantiles_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -515,6 +516,93 @@ def pred_score(state, dtype, obs=None, mask=None, extra_var=None, thr=(0.0,)):
         (C.c_double * nb)(*[float(x) for x in thr]), C.c_int(nb), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(table), _ptr(work)),
         "hode_pred_score")
     return out[0], out[1], out[2], table
+
+
+PRED_MAX_LEVELS, PRED_BAND_COLS = 16, 4
+
+
+def pred_tail_state(N, K, dtype, device):
+    """A fresh tail state of N entries that keeps the K smallest and the K largest values of each (include/hode.h "Posterior
+    bands"): cnt = 0; the buffers lo, hi [K, N] in `dtype` need no initialisation."""
+    _sfx(dtype)
+    if int(N) < 1 or int(K) < 1:
+        raise HodeError("pred_tail_state: N >= 1 and K >= 1")
+    return {"cnt": torch.zeros(int(N), dtype=torch.int32, device=device),
+            "lo": torch.empty(int(K), int(N), dtype=dtype, device=device), "hi": torch.empty(int(K), int(N), dtype=dtype, device=device)}
+
+
+def _pred_check_tail_state(tstate, what):
+    cnt, lo, hi = tstate["cnt"], tstate["lo"], tstate["hi"]
+    N = cnt.numel()
+    ok = cnt.dtype == torch.int32 and cnt.is_cuda and cnt.is_contiguous() and N >= 1 and lo.dim() == 2 and lo.shape[0] >= 1
+    ok = ok and lo.dtype in (torch.float32, torch.float64)
+    for t in (lo, hi):
+        ok = ok and t.dtype == lo.dtype and tuple(t.shape) == (lo.shape[0], N) and t.is_contiguous() and t.device == cnt.device
+    if not ok:
+        raise HodeError(f"{what}: the tail state must be contiguous device tensors cnt int32 [N], lo and hi [K, N] of one float dtype")
+    return N, lo.shape[0]
+
+
+def pred_tails(y, tstate, status=None):
+    """Take the draws y [n_draws, ...] (N entries each, in the dtype of the state's buffers, used where it lies when its rows are
+    dense) into the tail state (pred_tail_state) in draw order; status int32 [n_draws, n_traj] or None as in pred_fold."""
+    _need_gpu(y)
+    N, K = _pred_check_tail_state(tstate, "pred_tails")
+    S = y.shape[0]
+    if y.dim() < 2 or y.numel() != S * N or y.dtype != tstate["lo"].dtype or y.device != tstate["cnt"].device:
+        raise HodeError(f"pred_tails: y must be [n_draws, {N} entries] in the dtype and on the device of the state")
+    if not (y[0].is_contiguous() and (S == 1 or y.stride(0) == N)):
+        y = y.contiguous()
+    row_len = N
+    if status is not None:
+        status = status.to(device=y.device, dtype=torch.int32).contiguous()
+        if status.dim() != 2 or status.shape[0] != S or status.shape[1] < 1 or N % status.shape[1]:
+            raise HodeError("pred_tails: status must be [n_draws, n_traj] with n_traj dividing N")
+        row_len = N // status.shape[1]
+    _check(getattr(load(), f"hode_pred_tails_{_sfx(y.dtype)}")(
+        _stream(), C.c_int(S), C.c_int64(N), _ptr(y), _ptr(status), C.c_int64(row_len), C.c_int(K), _ptr(tstate["cnt"]),
+        _ptr(tstate["lo"]), _ptr(tstate["hi"])), "hode_pred_tails")
+
+
+def pred_quantiles(tstate, levels, obs=None, mask=None, band=False):
+    """The quantiles of a tail state at `levels` (host fractions strictly inside (0, 1), ascending, at most PRED_MAX_LEVELS):
+    returns (out [len(levels), N] in the state's dtype, band_table).  band=True also scores the band [levels[0], levels[-1]]
+    against obs [N] (mask uint8 [N] or None) into the fp64 table [6, PRED_BAND_COLS] of include/hode.h; otherwise band_table
+    is None.  The state's buffers are sorted in place and stay valid for further pred_tails calls."""
+    N, K = _pred_check_tail_state(tstate, "pred_quantiles")
+    dev, dtype = tstate["cnt"].device, tstate["lo"].dtype
+    lv = [float(q) for q in levels]
+    if not 1 <= len(lv) <= PRED_MAX_LEVELS:
+        raise HodeError(f"pred_quantiles: {len(lv)} levels, the kernel takes 1..{PRED_MAX_LEVELS} (HODE_PRED_MAX_LEVELS)")
+    if not all(0.0 < q < 1.0 for q in lv) or any(b <= a for a, b in zip(lv, lv[1:])):
+        raise HodeError("pred_quantiles: levels must lie strictly inside (0, 1) and ascend")
+    if obs is not None and (obs.dtype != dtype or obs.numel() != N or not obs.is_contiguous() or obs.device != dev):
+        raise HodeError("pred_quantiles: obs must be a contiguous device tensor of N entries in the state's dtype")
+    if mask is not None and (obs is None or mask.dtype != torch.uint8 or mask.numel() != N or not mask.is_contiguous()):
+        raise HodeError("pred_quantiles: mask must be uint8 with the shape of obs")
+    table = work = None
+    if band:
+        if obs is None or N % 6 or not lv[0] < 0.5 < lv[-1]:
+            raise HodeError("pred_quantiles: a band table needs obs, N % 6 == 0 and levels[0] < 1/2 < levels[-1]")
+        table = torch.empty(6, PRED_BAND_COLS, dtype=torch.float64, device=dev)
+        work = torch.empty(PRED_SCORE_BLOCKS * 6 * PRED_BAND_COLS, dtype=torch.float64, device=dev)
+    out = torch.empty(len(lv), N, dtype=dtype, device=dev)
+    _check(getattr(load(), f"hode_pred_quantiles_{_sfx(dtype)}")(
+        _stream(), C.c_int64(N), C.c_int(K), _ptr(tstate["cnt"]), _ptr(tstate["lo"]), _ptr(tstate["hi"]), C.c_int(len(lv)),
+        (C.c_double * len(lv))(*lv), _ptr(out), _ptr(obs), _ptr(mask), _ptr(table), _ptr(work)), "hode_pred_quantiles")
+    return out, table
+
+
+def pred_tail_values(tstate):
+    """(lower, upper), each [K, N], of a tail state that pred_quantiles has sorted: the min(cnt, K) smallest and the min(cnt, K)
+    largest values of every entry, ascending, NaN in the slots past them."""
+    _, K = _pred_check_tail_state(tstate, "pred_tail_values")
+    lo, hi = tstate["lo"], tstate["hi"]
+    m = tstate["cnt"].clamp(max=K).to(torch.int64).unsqueeze(0)                                   # values held per entry
+    r = torch.arange(K, device=lo.device).unsqueeze(1)                                            # ascending rank
+    nan = torch.full((), float("nan"), dtype=lo.dtype, device=lo.device)
+    # lo is sorted largest first, hi smallest first
+    return torch.where(r < m, lo.gather(0, (m - 1 - r).clamp(min=0)), nan), torch.where(r < m, hi, nan)
 
 
 def hmc_refresh(C_, D, ld, seed, it, jitter, minv, log_eps, z, g, U, p, z0, g0, U0, ke0, eps, failed):

@@ -275,7 +275,8 @@ class HMCResult:
     `stats`: accept_prob / log_posterior / divergent / failed_solve [chains, draws], step_size [chains], inv_mass [D];
     `rhat()` / `ess()`: split R-hat and multi-chain bulk ESS of every coordinate; `predict(...)`: posterior predictive;
     `noise_sigma(...)`: draws of the observation noise (inferred with noise="marginal", else the fixed values);
-    `predictive_summary(...)`: the posterior predictive folded into per-entry summaries and scored (inference/predictive.py)."""
+    `predictive_summary(...)`: the posterior predictive folded into per-entry summaries and scored (inference/predictive.py);
+    `summary()`: mean / std / median / q025 / q975 / rhat / ess of every parameter (the reference's posterior_summary)."""
 
     def __init__(self, draws, ode_names, nn_names, stats, model=None, ode_base=None, nn_base=None, observation=None, data=None):
         self.draws = draws                          # [C, n, D] natural coordinates (device or CPU tensor)
@@ -323,6 +324,38 @@ class HMCResult:
         rank-normalised draws (Vehtari et al. 2021), "mean" on the draws themselves (the ESS of the posterior mean's MCSE)."""
         x = self.draws.double()
         return _ess(_split(_rank_normal(x) if kind == "bulk" else x))
+
+    def summary(self) -> Dict[str, Dict[str, np.ndarray]]:
+        """The reference's posterior_summary of all chains' draws, keyed like `samples`: {name: {mean, std, median, q025, q975,
+        rhat, ess}}, each shaped like the parameter (std with ddof = 0, as np.std; the quantiles are numpy's "linear" ones; ess
+        is the bulk ESS).  The quantiles come from the tail kernels over the [chains * draws, D] block (hode.capi.pred_tails /
+        pred_quantiles, N = D); mean and std are fp64 on the device."""
+        from inference.predictive import tail_size
+        from models.hybrid_ode_nn import _compute_device
+        levels = (0.025, 0.5, 0.975)
+        x = self.draws.detach().to(_compute_device())
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float32)
+        x = x.reshape(-1, x.shape[2]).contiguous()
+        S, D = x.shape
+        ts = hode.capi.pred_tail_state(D, tail_size(levels, S), x.dtype, x.device)
+        hode.capi.pred_tails(x, ts)
+        q, _ = hode.capi.pred_quantiles(ts, levels)
+        xd = x.double()
+        flat = {"mean": xd.mean(0), "std": xd.std(0, unbiased=False), "q025": q[0], "median": q[1], "q975": q[2],
+                "rhat": self.rhat(), "ess": self.ess()}
+        flat = {k: v.detach().double().cpu().numpy() for k, v in flat.items()}
+        out, off = {}, 0
+        for name in self.ode_names:
+            out[f"ode.{name}"] = {k: v[off] for k, v in flat.items()}
+            off += 1
+        for name, shape in self.nn_names:
+            k = int(np.prod(shape))
+            if off + k > D:
+                break
+            out[f"nn.{name}"] = {key: v[off:off + k].reshape(shape) for key, v in flat.items()}
+            off += k
+        return out
 
     def _param_sets(self, thin=1):
         from models.ode_core import ODE_PARAM_NAMES
@@ -372,13 +405,14 @@ class HMCResult:
         return y.to(self.model.device)
 
     def predictive_summary(self, batch=None, thin=1, observation_noise=True, seed=0, n_bins=10, max_bytes=None, solver="dopri5",
-                           rtol=1e-6, atol=1e-8):
+                           rtol=1e-6, atol=1e-8, *, quantiles=None):
         """The posterior predictive of the kept draws (every `thin`-th of each chain, in `predict`'s order) on `batch` (default:
         the run's) as a `PredictiveSummary`: mean / std / PIT per entry and the scores against the batch's observations, folded
         piece by piece under max_bytes of trajectories instead of held as `predict`'s [n_draws, B, T, 6] block.
         observation_noise=True scores the predictive of the OBSERVATIONS: the draws of `noise_sigma(batch, thin, seed)` (the
         run's fixed values, or with noise="marginal" the inferred ones) enter the PIT, the log density and, by the law of total
-        variance, std.  Serves run_hmc and run_nuts alike (both return this class)."""
+        variance, std.  quantiles (fractions in (0, 1)): also the exact quantiles of the latent trajectories across the kept
+        draws (`PredictiveSummary.quantiles`, `.band()`).  Serves run_hmc and run_nuts alike (both return this class)."""
         from inference import predictive as PR
         if self.model is None:
             raise ValueError("this result carries no model (built from arrays)")
@@ -389,7 +423,7 @@ class HMCResult:
         sigma = self.noise_sigma(batch, thin, seed, solver, rtol, atol) if observation_noise else None
         return PR.predictive_summary(self.model, (nn_flat.view(S, -1), ode_vec.view(S, 17)), batch, sigma=sigma, n_bins=n_bins,
                                      max_bytes=PR._DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, solver=solver, rtol=rtol,
-                                     atol=atol)
+                                     atol=atol, quantiles=quantiles)
 
     def _solve_draws(self, initial_state, t_span, external_inputs, thin, solver, rtol, atol):
         """[n_draws, B, T, 6] on the compute device."""

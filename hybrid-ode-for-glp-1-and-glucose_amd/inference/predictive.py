@@ -8,7 +8,11 @@ the pointwise log density), a piece of draws at a time, so memory depends on one
 the state against the data in one deterministic pass and `PredictiveSummary.metrics()` names the sums.
 
 Folding the same draws in any split into consecutive `fold` calls gives bit-identical state (the kernel takes the draws one at
-a time in draw order and the state is fp64 in memory as in registers), so `max_bytes` changes memory and nothing else."""
+a time in draw order and the state is fp64 in memory as in registers), so `max_bytes` changes memory and nothing else.
+
+With `quantiles=` the fold also keeps the few smallest and largest values of every entry (`tail_size` of them: a tail quantile
+is interpolated between two order statistics near its end), and `finish` turns them into the exact empirical quantiles of the
+draws -- the credible bands of the reference's third figure -- again whatever the split."""
 import math
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -17,13 +21,15 @@ import torch
 
 import hode
 
-__all__ = ["PredictiveAccumulator", "PredictiveSummary", "predictive_summary", "cut_draws", "half_normal_thresholds", "STATE_NAMES",
-           "TABLE_COLUMNS"]
+__all__ = ["PredictiveAccumulator", "PredictiveSummary", "predictive_summary", "cut_draws", "half_normal_thresholds", "tail_size",
+           "STATE_NAMES", "TABLE_COLUMNS", "BAND_COLUMNS"]
 
 STATE_NAMES = ("glucose", "insulin", "glucagon", "glp1", "ge", "ffa")
 # the fixed columns of the score table (include/hode.h); the n_bins threshold counts and the n_bins PIT counts follow
 TABLE_COLUMNS = ("count", "sum_sq_err", "sum_abs_err", "sum_obs", "sum_obs_sq", "count_unc", "sum_sd", "sum_norm_err", "sum_interval_score",
                  "cover_50", "cover_80", "cover_90", "cover_95", "sum_crps", "sum_lppd", "count_lppd")
+# the columns of the band table (include/hode.h, "Posterior bands")
+BAND_COLUMNS = ("count", "sum_width", "cover", "sum_interval_score")
 _DEFAULT_MAX_BYTES = 256 << 20
 
 
@@ -44,6 +50,24 @@ def cut_draws(n_draws: int, bytes_per_draw: int, max_bytes: int) -> List[Tuple[i
     return [(lo, min(lo + per, n_draws)) for lo in range(0, n_draws, per)]
 
 
+def _levels(quantiles) -> List[float]:
+    lv = sorted({float(q) for q in quantiles})
+    if not lv or not all(0.0 < q < 1.0 for q in lv) or len(lv) > hode.capi.PRED_MAX_LEVELS:
+        raise ValueError(f"quantiles must be 1..{hode.capi.PRED_MAX_LEVELS} fractions strictly inside (0, 1)")
+    return lv
+
+
+def tail_size(levels: Sequence[float], n_draws: int) -> int:
+    """How many of the smallest and of the largest values of an entry the quantiles at `levels` (fractions in (0, 1)) of n_draws
+    draws need: the quantile q is interpolated between order statistics floor(q (n - 1)) and the next one, counted from the
+    nearer end, so min(n_draws, max over the levels of floor(min(q, 1 - q) (n_draws - 1)) + 2).  26 of 1 000 draws at 2.5 %."""
+    n = int(n_draws)
+    lv = [float(q) for q in levels]
+    if n < 1 or not lv or not all(0.0 < q < 1.0 for q in lv):
+        raise ValueError("tail_size: n_draws >= 1 and levels strictly inside (0, 1)")
+    return min(n, max(int(math.floor(min(q, 1.0 - q) * float(n - 1))) + 2 for q in lv))
+
+
 def _device():
     if not torch.cuda.is_available():
         raise hode.HodeError("predictive summaries need a HIP device: the fold and score kernels have no CPU fallback")
@@ -54,16 +78,65 @@ class PredictiveSummary:
     """What `PredictiveAccumulator.finish` returns: `mean`, `std`, `pit` (working precision) and `n` (int32), all [B, T, 6] on
     the device -- std is unbiased like torch.std plus the mean noise variance, NaN where fewer than two draws were folded; pit is
     the mean predictive CDF at the observation, NaN where unobserved -- `table` (fp64 numpy [6, 16 + 2 n_bins], the per-state
-    sums of include/hode.h, columns TABLE_COLUMNS then the threshold counts then the PIT histogram) and `metrics()`."""
+    sums of include/hode.h, columns TABLE_COLUMNS then the threshold counts then the PIT histogram) and `metrics()`.
 
-    def __init__(self, mean, std, pit, n, table, thresholds):
+    When the accumulator was given `quantiles`: `levels` (the requested fractions, ascending), `quantiles` [Q, B, T, 6] (the
+    exact empirical quantiles of the folded draws, numpy's "linear" method; NaN where no draw was folded), `band(level)`,
+    `tails()` and, when the outer levels enclose 1/2 and there are observations, `band_table` (fp64 numpy [6, 4], columns
+    BAND_COLUMNS) whose scores `metrics()` adds as band_width, band_coverage and band_interval_score.  Otherwise `levels` and
+    `quantiles` are None."""
+
+    def __init__(self, mean, std, pit, n, table, thresholds, levels=None, quantiles=None, band_table=None, tails=None):
         self.mean, self.std, self.pit, self.n = mean, std, pit, n
         self.table = np.asarray(table, dtype=np.float64)
         self.thresholds = list(thresholds)
         self.n_bins = len(self.thresholds)
+        self.levels = None if levels is None else list(levels)
+        self.quantiles = quantiles
+        self.band_table = None if band_table is None else np.asarray(band_table, dtype=np.float64)
+        self._tails = tails                            # a callable of the accumulator: the buffers are not copied
 
     def metrics(self) -> Dict[str, Union[float, np.ndarray]]:
-        return table_metrics(self.table, self.n_bins)
+        out = table_metrics(self.table, self.n_bins)
+        if self.band_table is not None:
+            out.update(band_metrics(self.band_table))
+        return out
+
+    def band(self, level: float = 0.95):
+        """(lower, upper), each [B, T, 6]: the central credible band of mass `level`, i.e. the quantiles 1/2 - level/2 and
+        1/2 + level/2, when that pair was requested; KeyError otherwise."""
+        if self.levels is None:
+            raise KeyError("no quantiles were requested")
+        pair = []
+        for q in (0.5 - 0.5 * float(level), 0.5 + 0.5 * float(level)):
+            hit = [i for i, have in enumerate(self.levels) if abs(have - q) <= 1e-12]
+            if not hit:
+                raise KeyError(f"quantile {q} was not requested (levels {self.levels})")
+            pair.append(self.quantiles[hit[0]])
+        return pair[0], pair[1]
+
+    def tails(self):
+        """(lower, upper), each [K, B, T, 6] ascending and NaN-padded at the end: the K smallest and the K largest values every
+        entry was given, i.e. the sorted contents of the accumulator's buffers (which this reads: it raises once the accumulator
+        has folded further draws)."""
+        if self._tails is None:
+            raise KeyError("no quantiles were requested")
+        return self._tails()
+
+
+def band_metrics(band_table: np.ndarray) -> Dict[str, Union[float, np.ndarray]]:
+    """The scores of a band table [6, 4] (BAND_COLUMNS): band_width, band_coverage and band_interval_score, pooled from the pooled
+    sums and per state under `<key>_per_state`; NaN where no entry was scored."""
+    t = np.asarray(band_table, dtype=np.float64)
+
+    def scores(r):
+        c = r[..., 0]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            over = lambda i: np.where(c > 0, r[..., i] / np.where(c > 0, c, 1.0), np.nan)                      # noqa: E731
+            return {"band_width": over(1), "band_coverage": over(2), "band_interval_score": over(3)}
+    out = {k: float(v) for k, v in scores(t.sum(0)).items()}
+    out.update({f"{k}_per_state": v for k, v in scores(t).items()})
+    return out
 
 
 def table_metrics(table: np.ndarray, n_bins: int) -> Dict[str, Union[float, np.ndarray]]:
@@ -111,9 +184,14 @@ def table_metrics(table: np.ndarray, n_bins: int) -> Dict[str, Union[float, np.n
 class PredictiveAccumulator:
     """The running state of n_traj x T x 6 entries on the device.  `fold(y, sigma=None, status=None)` adds draws,
     `finish(n_bins=10)` scores them.  observations [n_traj, T, 6] (NaN = missing) and observation_mask (bool, same shape) as in
-    inference/observation.py; without observations only mean / std / n are produced and the table is empty."""
+    inference/observation.py; without observations only mean / std / n are produced and the table is empty.
 
-    def __init__(self, n_traj: int, T: int, observations=None, observation_mask=None, dtype=torch.float32):
+    quantiles (keyword, fractions in (0, 1)) with expected_draws (the most draws that will be folded): `fold` also keeps the
+    tail_size(quantiles, expected_draws) smallest and largest values of every entry (hode.capi.pred_tails) and `finish` turns
+    them into the exact quantiles of the folded draws; like the rest of the state they do not depend on how the draws were cut."""
+
+    def __init__(self, n_traj: int, T: int, observations=None, observation_mask=None, dtype=torch.float32, *, quantiles=None,
+                 expected_draws: Optional[int] = None):
         if dtype not in (torch.float32, torch.float64):
             raise ValueError("dtype must be torch.float32 or torch.float64")
         if n_traj < 1 or T < 1:
@@ -137,6 +215,14 @@ class PredictiveAccumulator:
         self.state = hode.capi.pred_state(self.N, dev)
         self._var_sum = torch.zeros(6, dtype=torch.float64, device=dev)       # sum over the folded draws of sigma_k^2
         self.n_folded = 0
+        self.levels = self.tail_state = self.expected_draws = None
+        if quantiles is not None:
+            self.levels = _levels(quantiles)
+            if expected_draws is None or int(expected_draws) < 1:
+                raise ValueError("quantiles need expected_draws >= 1: the number of draws that will be folded sizes the buffers")
+            self.expected_draws = int(expected_draws)
+            self.tail_state = hode.capi.pred_tail_state(self.N, tail_size(self.levels, self.expected_draws), dtype, dev)
+        self._tail_version = 0
 
     @classmethod
     def from_moments(cls, predictions, uncertainties, observations, observation_mask=None, dtype=None):
@@ -186,7 +272,11 @@ class PredictiveAccumulator:
         sig = self._sigma(sigma, S)
         if status is not None:
             status = torch.as_tensor(status).reshape(S, self.n_traj)
-        hode.capi.pred_fold(y.reshape(S, self.N) if y.is_contiguous() else y, self.state, self.obs, self.mask, sig, status)
+        y = y.reshape(S, self.N) if y.is_contiguous() else y
+        hode.capi.pred_fold(y, self.state, self.obs, self.mask, sig, status)
+        if self.tail_state is not None:
+            hode.capi.pred_tails(y, self.tail_state, status)
+            self._tail_version += 1
         if sig is not None:
             self._var_sum += (sig * sig).sum(0)
         self.n_folded += S
@@ -199,8 +289,27 @@ class PredictiveAccumulator:
         extra = (self._var_sum / max(self.n_folded, 1)).tolist()
         mean, sd, pit, table = hode.capi.pred_score(self.state, self.dtype, self.obs, self.mask, extra, thr)
         shape = (self.n_traj, self.T, 6)
+        extra = {}
+        if self.tail_state is not None:
+            if self.n_folded > self.expected_draws:
+                raise ValueError(f"{self.n_folded} draws were folded but the quantile buffers were sized for expected_draws = "
+                                 f"{self.expected_draws}")
+            band = self.obs is not None and self.levels[0] < 0.5 < self.levels[-1]
+            q, bt = hode.capi.pred_quantiles(self.tail_state, self.levels, self.obs if band else None, self.mask if band else None, band)
+            extra = dict(levels=self.levels, quantiles=q.view(len(self.levels), *shape), band_table=None if bt is None else bt.cpu().numpy(),
+                         tails=self._tails_reader())
         return PredictiveSummary(mean.view(shape), sd.view(shape), pit.view(shape), self.state["n"].view(shape).clone(),
-                                 table.cpu().numpy(), thr)
+                                 table.cpu().numpy(), thr, **extra)
+
+    def _tails_reader(self):
+        version = self._tail_version
+
+        def read():
+            if version != self._tail_version:
+                raise RuntimeError("the accumulator has folded further draws since this summary was made: call finish() again")
+            lower, upper = hode.capi.pred_tail_values(self.tail_state)                            # (finish() sorted the buffers)
+            return lower.view(-1, self.n_traj, self.T, 6), upper.view(-1, self.n_traj, self.T, 6)
+        return read
 
 
 def _rep_inputs(S, x0, t_span, external_inputs):
@@ -216,13 +325,15 @@ def _rep_inputs(S, x0, t_span, external_inputs):
 
 def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None, n_bins: int = 10,
                        max_bytes: int = _DEFAULT_MAX_BYTES, solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8,
-                       dtype=torch.float32) -> PredictiveSummary:
+                       dtype=torch.float32, *, quantiles=None) -> PredictiveSummary:
     """The posterior-predictive summary of `draws` on `batch` {initial_state, time_points[, observations, observation_mask,
     external_inputs]}.  draws: a list of named parameter overrides (what `variational_params.sample` and `forward_param_sets`
     take), or a pair (nn_flat [S, P], ode_vec [S, 17]) of parameter tensors.  sigma: the observation noise, None, a scalar, six
     values or one row of six per draw.  The draws are cut into pieces whose trajectories fit max_bytes (`cut_draws`), each piece
     is ONE batched solve (no tape) and is folded with the solve's statuses before the next one starts: no more than one
-    piece of trajectories exists at a time, and the result does not depend on the cut."""
+    piece of trajectories exists at a time, and the result does not depend on the cut.  quantiles (fractions in (0, 1), e.g.
+    (0.025, 0.975) for the 95 % credible band): also the exact empirical quantiles of the LATENT trajectories across the draws,
+    `PredictiveSummary.quantiles` / `.band()`; sigma does not enter them."""
     from models.hybrid_ode_nn import _compute_device
     dev = _compute_device()
     x0 = batch["initial_state"]
@@ -232,7 +343,8 @@ def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None,
     T = t.shape[-1]
     named = not (isinstance(draws, tuple) and len(draws) == 2 and isinstance(draws[0], torch.Tensor))
     S = len(draws) if named else draws[0].shape[0]
-    acc = PredictiveAccumulator(B, T, batch.get("observations"), batch.get("observation_mask"), dtype)
+    acc = PredictiveAccumulator(B, T, batch.get("observations"), batch.get("observation_mask"), dtype, quantiles=quantiles,
+                                expected_draws=None if quantiles is None else max(S, 1))
     sig = acc._sigma(sigma, S)
     for lo, hi in cut_draws(S, B * T * 6 * 4, max_bytes):                         # (the solve's trajectories are fp32)
         n = hi - lo

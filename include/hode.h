@@ -590,6 +590,60 @@ int hode_pred_score_f64(void *stream, int64_t N, const int32_t *n, const double 
                         const double *lmax, const double *lsum, const double *obs, const uint8_t *mask, const double *extra_var,
                         const double *thr, int n_bins, double *out_mean, double *out_sd, double *out_pit, double *table, double *work);
 
+/* =====================================================================================================
+ * Posterior bands: exact tail quantiles across the draws (inference/predictive.py `quantiles=`, HMCResult.summary): what the
+ * reference's np.percentile(draws, 2.5 / 97.5, axis=0) and posterior_summary compute from the stack of draws, without the
+ * stack.  The quantile q of n values is interpolated between order statistics floor(q (n - 1)) and the next one, so only the
+ * K = floor(min(q, 1 - q) (n - 1)) + 2 smallest (q <= 1/2) or largest values of an entry matter.
+ *
+ * The tail state of N entries (ANY N >= 1: an entry is one element of y, no state index is used), DEVICE memory the caller
+ * owns, R the working precision:
+ *   cnt   int32[N]   draws taken so far
+ *   lo    R[K][N]    the min(cnt, K) smallest values taken, slot j of entry i at j * N + i
+ *   hi    R[K][N]    the min(cnt, K) largest values taken, the same layout
+ * A fresh state is cnt = 0; lo and hi need no initialisation.  The order of the values inside a buffer is the library's
+ * business (lo is a binary max-heap, hi a min-heap: slot 0 is the largest of lo and the smallest of hi).
+ *
+ * hode_pred_tails_* takes n_draws more draws y[n_draws][N], ONE AT A TIME IN DRAW ORDER, per entry, with the skip rules of
+ * hode_pred_fold_*: the draw is skipped when status[s][i / row_len] != 0 (status: int32[n_draws][N / row_len], NULL = all
+ * fine) or when y is not finite; else, while cnt < K, y enters both buffers, and after that it replaces the largest of lo
+ * when y < it and the smallest of hi when it < y; cnt += 1.  Values are copied and compared with <, never computed with.
+ * A draw is a pure update of the state in memory: any split of the draws into consecutive calls leaves bit-identical state,
+ * and any permutation of the draws leaves the same multiset in each buffer (+0.0 and -0.0 compare equal: which of the two
+ * is kept may depend on the order).  A lane owns one entry (no reduction, no atomics); a value that enters a buffer costs
+ * O(log K) loads and stores, any other its load and two compares.  K is a run-time argument without a cap.
+ * HODE_EINVAL: n_draws < 0, N < 1, K < 1, a NULL state pointer, y NULL with n_draws > 0, with status a row_len < 1 or one
+ * that does not divide N.  n_draws == 0 is a no-op without a launch.
+ *
+ * hode_pred_quantiles_* reads a tail state and writes out[n_levels][N] (R) for levels (HOST double[n_levels], strictly
+ * inside (0, 1), ascending, n_levels in 1..HODE_PRED_MAX_LEVELS): numpy's default "linear" quantile.  With n = cnt[i]:
+ *   h = q (double)(n - 1);  j = floor(h);  g = h - j;  out = a + (b - a) g
+ * a, b the order statistics j and min(j + 1, n - 1) (ascending, from 0), read from lo when q <= 1/2 and from hi otherwise, in
+ * fp64 without contraction, rounded once to R.  out is NaN where n == 0 and where a needed order statistic is not in the
+ * buffer: with n > K, j + 1 >= K for q <= 1/2 and n - 1 - j >= K for q > 1/2.
+ * The call SORTS lo and hi in place (lo largest first, hi smallest first).  A sorted buffer is still a valid heap, so
+ * hode_pred_tails_* may go on folding into the state afterwards; that is why lo and hi are not const here.
+ * band_table: DEVICE double[6][HODE_PRED_BAND_COLS] or NULL.  It needs N % 6 == 0 (the state of entry i is i % 6), obs, work
+ * (DEVICE double[HODE_PRED_SCORE_BLOCKS * 6 * HODE_PRED_BAND_COLS], scratch space) and levels[0] < 1/2 < levels[n_levels - 1].
+ * With lo = out[0][i], hi = out[n_levels - 1][i] as written (R) and alpha = 1 - (levels[n_levels - 1] - levels[0]), per
+ * state over the OBSERVED entries (obs, mask as above) with n >= 2 and both bounds finite:
+ *   0 count   1 sum (hi - lo)   2 count of lo <= obs <= hi (inclusive)
+ *   3 sum of the interval score (hi - lo) + (2 / alpha) ((lo - obs)+ + (obs - hi)+)
+ * reduced in the fixed order of hode_pred_score_*: the same call gives the same bits.
+ * HODE_EINVAL: N < 1, K < 1, a NULL among cnt, lo, hi, levels and out, n_levels outside its range, a level outside (0, 1)
+ * or not above its predecessor, a mask without obs, a band_table without what it needs.
+ * ===================================================================================================== */
+#define HODE_PRED_MAX_LEVELS 16
+#define HODE_PRED_BAND_COLS 4
+int hode_pred_tails_f32(void *stream, int n_draws, int64_t N, const float *y, const int32_t *status, int64_t row_len, int K, int32_t *cnt,
+                        float *lo, float *hi);
+int hode_pred_tails_f64(void *stream, int n_draws, int64_t N, const double *y, const int32_t *status, int64_t row_len, int K, int32_t *cnt,
+                        double *lo, double *hi);
+int hode_pred_quantiles_f32(void *stream, int64_t N, int K, const int32_t *cnt, float *lo, float *hi, int n_levels, const double *levels,
+                            float *out, const float *obs, const uint8_t *mask, double *band_table, double *work);
+int hode_pred_quantiles_f64(void *stream, int64_t N, int K, const int32_t *cnt, double *lo, double *hi, int n_levels, const double *levels,
+                            double *out, const double *obs, const uint8_t *mask, double *band_table, double *work);
+
 #ifdef __cplusplus
 }
 #endif
