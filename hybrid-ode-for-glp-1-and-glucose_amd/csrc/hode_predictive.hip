@@ -24,15 +24,14 @@
 //               go on) and interpolates every level between two order statistics in fp64 (numpy's "linear" method); the band
 //               table [6][4] of the outer pair of levels against the data is reduced as the score table is.
 // There are no floating-point atomics in this file: the same call gives the same bits.
-#include "hode_chains.h"
+#include "hode_pred_heap.h"
 
 namespace hode {
 namespace {
 
 constexpr int kScoreBlocks = HODE_PRED_SCORE_BLOCKS;
 constexpr int kFixedCols = HODE_PRED_FIXED_COLS;
-constexpr double kInvSqrt2 = 0.70710678118654752440, kHalfLog2Pi = 0.91893853320467274178, kInvSqrtPi = 0.56418958354775628695,
-                 kInvSqrt2Pi = 0.39894228040143267794;
+constexpr double kInvSqrt2 = 0.70710678118654752440, kInvSqrtPi = 0.56418958354775628695, kInvSqrt2Pi = 0.39894228040143267794;
 
 template <typename R> struct FoldArgs {
     int n_draws;
@@ -44,8 +43,6 @@ template <typename R> struct FoldArgs {
     int32_t *n;
     double *mean, *m2, *pit, *lmax, *lsum;
 };
-
-template <typename R> __device__ __forceinline__ bool seen(R o, unsigned m) { return m != 0u && __builtin_isfinite(o); }
 
 // G consecutive values (G = 12 or 6) from p + i: 16-byte accesses when VEC (then G = 12 and p + i is 16-byte aligned)
 template <typename V, int G, bool VEC> __device__ __forceinline__ void ldg(const V *p, int64_t i, V (&o)[G])
@@ -350,16 +347,6 @@ template <typename R, bool VEC> __global__ __launch_bounds__(kThreads) void pred
         row[(i / (2 * a.n_bins)) * a.K + kFixedCols + i % (2 * a.n_bins)] = (double)hist[i];
 }
 
-// table[k][c] = the partial rows added in index order
-__global__ __launch_bounds__(kThreads) void pred_score_finish_kernel(int n_rows, int len, const double *work, double *table)
-{
-    for (int i = threadIdx.x; i < len; i += kThreads) {
-        double t = 0.0;
-        for (int r = 0; r < n_rows; ++r) t += work[(int64_t)r * len + i];
-        table[i] = t;
-    }
-}
-
 template <typename R>
 int pred_score(void *stream, int64_t N, const int32_t *n, const double *mean, const double *m2, const double *pit, const double *lmax,
                const double *lsum, const R *obs, const uint8_t *mask, const double *extra_var, const double *thr, int n_bins,
@@ -397,46 +384,6 @@ template <typename R> struct TailArgs {
     int32_t *cnt;
     R *lo, *hi;
 };
-
-// heap order: in a max-heap a parent is not below its children, in a min-heap not above.  `max` is a run-time value so that
-// the lanes of a wave that walk lo and the lanes that walk hi share one loop
-template <typename R> __device__ __forceinline__ bool below(bool max, R a, R b) { return max ? a < b : b < a; }
-
-// v into the hole at slot p of entry i's heap, the hole rising while its parent is below v
-template <typename R> __device__ __forceinline__ void sift_up(R *h, bool max, int64_t N, int64_t i, int64_t p, R v)
-{
-    while (p > 0) {
-        const int64_t q = (p - 1) >> 1;
-        const R u = h[q * N + i];
-        if (!below(max, u, v)) break;
-        h[p * N + i] = u;
-        p = q;
-    }
-    h[p * N + i] = v;
-}
-
-// v into the hole at the root of entry i's heap of `size` slots, the hole sinking while v is below its greater child;
-// returns the new root
-template <typename R> __device__ __forceinline__ R sift_down(R *h, bool max, int64_t N, int64_t i, int64_t size, R v)
-{
-    int64_t p = 0;
-    R root = v;
-    for (;;) {
-        int64_t c = 2 * p + 1;
-        if (c >= size) break;
-        R u = h[c * N + i];
-        if (c + 1 < size) {
-            const R w = h[(c + 1) * N + i];
-            if (below(max, u, w)) { u = w; c += 1; }
-        }
-        if (!below(max, v, u)) break;
-        h[p * N + i] = u;
-        if (p == 0) root = u;
-        p = c;
-    }
-    h[p * N + i] = v;
-    return root;
-}
 
 // One lane, one entry, all draws of the call, as pred_fold_kernel.  cnt and the two roots stay in registers; a draw that
 // passes neither root (all but about K (1 + ln(S / K)) of S draws per tail) costs its load and two compares.
@@ -514,22 +461,6 @@ template <typename R> struct QuantArgs {
     double levels[HODE_PRED_MAX_LEVELS];
     R *out;
 };
-
-// entry i's heap of m slots sorted in place, greatest first for a max-heap and least first for a min-heap (so it is still a
-// heap): heapsort leaves the opposite order, which is then reversed
-template <typename R> __device__ __forceinline__ void sort_heap(R *h, bool max, int64_t N, int64_t i, int64_t m)
-{
-    for (int64_t end = m - 1; end > 0; --end) {
-        const R v = h[end * N + i];
-        h[end * N + i] = h[i];
-        sift_down(h, max, N, i, end, v);
-    }
-    for (int64_t l = 0, r = m - 1; l < r; ++l, --r) {
-        const R u = h[l * N + i], w = h[r * N + i];
-        h[l * N + i] = w;
-        h[r * N + i] = u;
-    }
-}
 
 // One lane, one entry: sort both buffers, then numpy's "linear" quantile of every level from the nearer one.
 template <typename R> __global__ __launch_bounds__(kThreads) void pred_quantiles_kernel(const QuantArgs<R> a)

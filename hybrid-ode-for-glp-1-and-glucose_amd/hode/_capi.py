@@ -30,7 +30,8 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_nuts_post_f64", "hode_nuts_compact", "hode_nuts_finish_f32", "hode_nuts_finish_f64",
            "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64", "hode_sobol_indices_f32", "hode_sobol_indices_f64",
            "hode_pred_fold_f32", "hode_pred_fold_f64", "hode_pred_score_f32", "hode_pred_score_f64",
-           "hode_pred_tails_f32", "hode_pred_tails_f64", "hode_pred_quantiles_f32", "hode_pred_quantiles_f64"]
+           "hode_pred_tails_f32", "hode_pred_tails_f64", "hode_pred_quantiles_f32", "hode_pred_quantiles_f64",
+           "hode_pred_loo_fold_f32", "hode_pred_loo_fold_f64", "hode_pred_loo_finish_f32", "hode_pred_loo_finish_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -603,6 +604,104 @@ def pred_tail_values(tstate):
     nan = torch.full((), float("nan"), dtype=lo.dtype, device=lo.device)
     # lo is sorted largest first, hi smallest first
     return torch.where(r < m, lo.gather(0, (m - 1 - r).clamp(min=0)), nan), torch.where(r < m, hi, nan)
+
+
+PRED_LOO_COLS = 13
+PRED_LOO_STATE = ("cnt", "lmean", "lm2", "pmax", "psum", "top", "rmax", "rsum")
+PRED_LOO_OUTPUTS = ("elpd_loo", "pareto_k", "elpd_waic", "p_waic", "lppd")
+
+
+def pred_loo_state(N, K, device):
+    """A fresh LOO state of N entries that keeps the K largest log importance ratios of each (include/hode.h "Model
+    comparison"): all zero except pmax = rmax = -inf; top [K, N] needs no initialisation."""
+    N, K = int(N), int(K)
+    if N < 6 or N % 6 or K < 2:
+        raise HodeError("pred_loo_state: N a positive multiple of 6 and K >= 2")
+    z = lambda: torch.zeros(N, dtype=torch.float64, device=device)                               # noqa: E731
+    ninf = lambda: torch.full((N,), float("-inf"), dtype=torch.float64, device=device)           # noqa: E731
+    return {"cnt": torch.zeros(N, dtype=torch.int32, device=device), "lmean": z(), "lm2": z(), "pmax": ninf(), "psum": z(),
+            "top": torch.empty(K, N, dtype=torch.float64, device=device), "rmax": ninf(), "rsum": z()}
+
+
+def _pred_check_loo_state(lstate, what):
+    cnt, top = lstate["cnt"], lstate["top"]
+    N = cnt.numel()
+    ok = cnt.dtype == torch.int32 and cnt.is_cuda and cnt.is_contiguous() and top.dim() == 2
+    for k in PRED_LOO_STATE[1:]:
+        t = lstate[k]
+        ok = ok and t.dtype == torch.float64 and t.is_contiguous() and t.device == cnt.device
+        ok = ok and (tuple(t.shape) == (top.shape[0], N) if k == "top" else t.numel() == N)
+    if not ok or N < 6 or N % 6 or top.shape[0] < 2:
+        raise HodeError(f"{what}: the LOO state must be contiguous device tensors cnt int32 [N], top float64 [K, N] and six float64 [N], "
+                        "N a multiple of 6 and K >= 2")
+    return N, top.shape[0]
+
+
+def pred_loo_fold(y, lstate, obs, mask, sigma, status=None):
+    """Fold the pointwise log likelihood of the draws y [n_draws, ...] (N entries each, fp32 or fp64, used where it lies when its
+    rows are dense) into the LOO state (pred_loo_state) in draw order; obs [N] in y's dtype, mask uint8 [N] or None, sigma fp64
+    [n_draws, 6] and status int32 [n_draws, n_traj] or None as in pred_fold -- but obs and sigma are required."""
+    _need_gpu(y)
+    N, K = _pred_check_loo_state(lstate, "pred_loo_fold")
+    S = y.shape[0]
+    if y.dim() < 2 or y.numel() != S * N or y.device != lstate["cnt"].device:
+        raise HodeError(f"pred_loo_fold: y must be [n_draws, {N} entries] on the device of the state")
+    if not (y[0].is_contiguous() and (S == 1 or y.stride(0) == N)):
+        y = y.contiguous()
+    if obs is None or sigma is None:
+        raise HodeError("pred_loo_fold: obs and sigma are required (without observation noise there is no likelihood)")
+    if obs.dtype != y.dtype or obs.numel() != N or not obs.is_contiguous() or obs.device != y.device:
+        raise HodeError("pred_loo_fold: obs must be a contiguous device tensor of N entries in y's dtype")
+    if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != N or not mask.is_contiguous()):
+        raise HodeError("pred_loo_fold: mask must be uint8 with the shape of obs")
+    sigma = sigma.to(device=y.device, dtype=torch.float64).contiguous()
+    if tuple(sigma.shape) != (S, 6):
+        raise HodeError("pred_loo_fold: sigma must be [n_draws, 6]")
+    row_len = N
+    if status is not None:
+        status = status.to(device=y.device, dtype=torch.int32).contiguous()
+        if status.dim() != 2 or status.shape[0] != S or status.shape[1] < 1 or N % status.shape[1]:
+            raise HodeError("pred_loo_fold: status must be [n_draws, n_traj] with n_traj dividing N")
+        row_len = N // status.shape[1]
+    _check(getattr(load(), f"hode_pred_loo_fold_{_sfx(y.dtype)}")(
+        _stream(), C.c_int(S), C.c_int64(N), _ptr(y), _ptr(obs), _ptr(mask), _ptr(sigma), _ptr(status), C.c_int64(row_len), C.c_int(K),
+        *[_ptr(lstate[k]) for k in PRED_LOO_STATE]), "hode_pred_loo_fold")
+
+
+def pred_loo_fit_rows(K):
+    """Rows of the finish's scratch buffer fit[rows][N] for a state of K slots: (K - 1) + 30 + floor(sqrt(K - 1))."""
+    import math
+    return (int(K) - 1) + 30 + math.isqrt(int(K) - 1)
+
+
+def pred_loo_finish(lstate, dtype, r_eff=1.0):
+    """PSIS-LOO and WAIC of a LOO state: returns ({elpd_loo, pareto_k, elpd_waic, p_waic, lppd}, each [N] in `dtype`, NaN where
+    undefined, and the table fp64 [6, PRED_LOO_COLS] of include/hode.h).  r_eff: the relative efficiency of the draws, a host
+    scalar in (0, 1].  The state's top is sorted in place and stays valid for further pred_loo_fold calls."""
+    N, K = _pred_check_loo_state(lstate, "pred_loo_finish")
+    _sfx(dtype)
+    r_eff = float(r_eff)
+    if not 0.0 < r_eff <= 1.0:
+        raise HodeError("pred_loo_finish: r_eff must lie in (0, 1]")
+    dev = lstate["cnt"].device
+    out = {k: torch.empty(N, dtype=dtype, device=dev) for k in PRED_LOO_OUTPUTS}
+    table = torch.empty(6, PRED_LOO_COLS, dtype=torch.float64, device=dev)
+    fit = torch.empty(pred_loo_fit_rows(K), N, dtype=torch.float64, device=dev)
+    work = torch.empty(PRED_SCORE_BLOCKS * 6 * PRED_LOO_COLS, dtype=torch.float64, device=dev)
+    _check(getattr(load(), f"hode_pred_loo_finish_{_sfx(dtype)}")(
+        _stream(), C.c_int64(N), C.c_int(K), C.c_double(r_eff), *[_ptr(lstate[k]) for k in PRED_LOO_STATE],
+        *[_ptr(out[k]) for k in PRED_LOO_OUTPUTS], _ptr(table), _ptr(fit), _ptr(work)), "hode_pred_loo_finish")
+    return out, table
+
+
+def pred_loo_top_values(lstate):
+    """[K, N]: the min(cnt, K) largest log importance ratios of every entry of a state that pred_loo_finish has sorted, ascending,
+    NaN in the slots past them."""
+    _, K = _pred_check_loo_state(lstate, "pred_loo_top_values")
+    top = lstate["top"]
+    m = lstate["cnt"].clamp(max=K).to(torch.int64).unsqueeze(0)
+    r = torch.arange(K, device=top.device).unsqueeze(1)
+    return torch.where(r < m, top, torch.full((), float("nan"), dtype=top.dtype, device=top.device))
 
 
 def hmc_refresh(C_, D, ld, seed, it, jitter, minv, log_eps, z, g, U, p, z0, g0, U0, ke0, eps, failed):

@@ -405,25 +405,29 @@ class HMCResult:
         return y.to(self.model.device)
 
     def predictive_summary(self, batch=None, thin=1, observation_noise=True, seed=0, n_bins=10, max_bytes=None, solver="dopri5",
-                           rtol=1e-6, atol=1e-8, *, quantiles=None):
+                           rtol=1e-6, atol=1e-8, *, quantiles=None, loo=False, r_eff=1.0):
         """The posterior predictive of the kept draws (every `thin`-th of each chain, in `predict`'s order) on `batch` (default:
         the run's) as a `PredictiveSummary`: mean / std / PIT per entry and the scores against the batch's observations, folded
         piece by piece under max_bytes of trajectories instead of held as `predict`'s [n_draws, B, T, 6] block.
         observation_noise=True scores the predictive of the OBSERVATIONS: the draws of `noise_sigma(batch, thin, seed)` (the
         run's fixed values, or with noise="marginal" the inferred ones) enter the PIT, the log density and, by the law of total
         variance, std.  quantiles (fractions in (0, 1)): also the exact quantiles of the latent trajectories across the kept
-        draws (`PredictiveSummary.quantiles`, `.band()`).  Serves run_hmc and run_nuts alike (both return this class)."""
+        draws (`PredictiveSummary.quantiles`, `.band()`).  loo=True (needs observation_noise=True): also PSIS-LOO and WAIC of the
+        pointwise log likelihood, `PredictiveSummary.loo`, for `inference.compare`; r_eff: the relative efficiency of the kept
+        draws (1 = independent).  Serves run_hmc and run_nuts alike (both return this class)."""
         from inference import predictive as PR
         if self.model is None:
             raise ValueError("this result carries no model (built from arrays)")
         batch = self.data if batch is None else batch
         if batch is None:
             raise ValueError("predictive_summary needs a batch: the run had none")
+        if loo and not observation_noise:
+            raise ValueError("loo needs observation_noise=True: without observation noise there is no likelihood")
         S, nn_flat, ode_vec = self._param_sets(thin)
         sigma = self.noise_sigma(batch, thin, seed, solver, rtol, atol) if observation_noise else None
         return PR.predictive_summary(self.model, (nn_flat.view(S, -1), ode_vec.view(S, 17)), batch, sigma=sigma, n_bins=n_bins,
                                      max_bytes=PR._DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, solver=solver, rtol=rtol,
-                                     atol=atol, quantiles=quantiles)
+                                     atol=atol, quantiles=quantiles, loo=loo, r_eff=r_eff)
 
     def _solve_draws(self, initial_state, t_span, external_inputs, thin, solver, rtol, atol):
         """[n_draws, B, T, 6] on the compute device."""

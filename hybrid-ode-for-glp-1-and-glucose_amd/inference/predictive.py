@@ -12,7 +12,12 @@ a time in draw order and the state is fp64 in memory as in registers), so `max_b
 
 With `quantiles=` the fold also keeps the few smallest and largest values of every entry (`tail_size` of them: a tail quantile
 is interpolated between two order statistics near its end), and `finish` turns them into the exact empirical quantiles of the
-draws -- the credible bands of the reference's third figure -- again whatever the split."""
+draws -- the credible bands of the reference's third figure -- again whatever the split.
+
+With `loo=True` the fold also keeps, per observed entry, what Pareto-smoothed importance-sampling leave-one-out cross-validation
+and WAIC need of the pointwise log likelihood -- its `loo_tail_size` largest importance ratios and running sums over the rest
+(csrc/hode_loo.hip) -- and `finish` turns them into `PredictiveSummary.loo`, a `LooResult`; `compare` ranks fitted models by
+it."""
 import math
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -22,7 +27,7 @@ import torch
 import hode
 
 __all__ = ["PredictiveAccumulator", "PredictiveSummary", "predictive_summary", "cut_draws", "half_normal_thresholds", "tail_size",
-           "STATE_NAMES", "TABLE_COLUMNS", "BAND_COLUMNS"]
+           "loo_tail_size", "LooResult", "compare", "STATE_NAMES", "TABLE_COLUMNS", "BAND_COLUMNS", "LOO_COLUMNS"]
 
 STATE_NAMES = ("glucose", "insulin", "glucagon", "glp1", "ge", "ffa")
 # the fixed columns of the score table (include/hode.h); the n_bins threshold counts and the n_bins PIT counts follow
@@ -30,6 +35,9 @@ TABLE_COLUMNS = ("count", "sum_sq_err", "sum_abs_err", "sum_obs", "sum_obs_sq", 
                  "cover_50", "cover_80", "cover_90", "cover_95", "sum_crps", "sum_lppd", "count_lppd")
 # the columns of the band table (include/hode.h, "Posterior bands")
 BAND_COLUMNS = ("count", "sum_width", "cover", "sum_interval_score")
+# the columns of the LOO table (include/hode.h, "Model comparison")
+LOO_COLUMNS = ("count", "sum_elpd_loo", "sum_elpd_loo_sq", "sum_p_loo", "sum_elpd_waic", "sum_elpd_waic_sq", "sum_p_waic", "sum_lppd",
+               "k_good", "k_ok", "k_bad", "k_very_bad", "p_waic_large")
 _DEFAULT_MAX_BYTES = 256 << 20
 
 
@@ -68,6 +76,16 @@ def tail_size(levels: Sequence[float], n_draws: int) -> int:
     return min(n, max(int(math.floor(min(q, 1.0 - q) * float(n - 1))) + 2 for q in lv))
 
 
+def loo_tail_size(n_draws: int, r_eff: float = 1.0) -> int:
+    """How many of the largest importance ratios of an entry PSIS needs of n_draws draws: M + 1 with the tail length
+    M = ceil(min(n / 5, 3 sqrt(n / r_eff))) of Vehtari et al. 2024 (the extra one is the cut).  53 of 300 draws, 97 of 1 024.
+    The kernel computes the same M in the same fp64 arithmetic from the draws it actually counted."""
+    n, r = int(n_draws), float(r_eff)
+    if n < 1 or not 0.0 < r <= 1.0:
+        raise ValueError("loo_tail_size: n_draws >= 1 and r_eff in (0, 1]")
+    return int(math.ceil(min(float(n) / 5.0, 3.0 * math.sqrt(float(n) / r)))) + 1
+
+
 def _device():
     if not torch.cuda.is_available():
         raise hode.HodeError("predictive summaries need a HIP device: the fold and score kernels have no CPU fallback")
@@ -84,9 +102,9 @@ class PredictiveSummary:
     exact empirical quantiles of the folded draws, numpy's "linear" method; NaN where no draw was folded), `band(level)`,
     `tails()` and, when the outer levels enclose 1/2 and there are observations, `band_table` (fp64 numpy [6, 4], columns
     BAND_COLUMNS) whose scores `metrics()` adds as band_width, band_coverage and band_interval_score.  Otherwise `levels` and
-    `quantiles` are None."""
+    `quantiles` are None.  `loo` is a `LooResult` when the accumulator was given loo=True, else None."""
 
-    def __init__(self, mean, std, pit, n, table, thresholds, levels=None, quantiles=None, band_table=None, tails=None):
+    def __init__(self, mean, std, pit, n, table, thresholds, levels=None, quantiles=None, band_table=None, tails=None, loo=None):
         self.mean, self.std, self.pit, self.n = mean, std, pit, n
         self.table = np.asarray(table, dtype=np.float64)
         self.thresholds = list(thresholds)
@@ -95,6 +113,7 @@ class PredictiveSummary:
         self.quantiles = quantiles
         self.band_table = None if band_table is None else np.asarray(band_table, dtype=np.float64)
         self._tails = tails                            # a callable of the accumulator: the buffers are not copied
+        self.loo = loo                                 # a LooResult when the accumulator was given loo=True
 
     def metrics(self) -> Dict[str, Union[float, np.ndarray]]:
         out = table_metrics(self.table, self.n_bins)
@@ -122,6 +141,91 @@ class PredictiveSummary:
         if self._tails is None:
             raise KeyError("no quantiles were requested")
         return self._tails()
+
+
+class LooResult:
+    """PSIS-LOO and WAIC of one fitted model on one data set: the pointwise `elpd_loo`, `pareto_k`, `elpd_waic`, `p_waic`, `lppd`
+    ([B, T, 6] device tensors in the working precision, NaN where the entry is unobserved, has no observation noise or fewer
+    than two draws), `table` (fp64 numpy [6, 13], columns LOO_COLUMNS, per-state sums of the fp64 values) and `estimates()`.
+    `r_eff` is the relative efficiency the tail length was computed with."""
+
+    def __init__(self, elpd_loo, pareto_k, elpd_waic, p_waic, lppd, table, r_eff=1.0):
+        self.elpd_loo, self.pareto_k, self.elpd_waic, self.p_waic, self.lppd = elpd_loo, pareto_k, elpd_waic, p_waic, lppd
+        self.table = np.asarray(table, dtype=np.float64)
+        if self.table.shape != (6, len(LOO_COLUMNS)):
+            raise ValueError(f"table must be [6, {len(LOO_COLUMNS)}]")
+        self.r_eff = float(r_eff)
+
+    def estimates(self) -> Dict[str, Union[float, np.ndarray]]:
+        """elpd_loo (the SUM over the scored entries), se = sqrt(count * var) of the pointwise values (ddof 0, as arviz), p_loo,
+        looic = -2 elpd_loo; elpd_waic, se_waic, p_waic, waic = -2 elpd_waic; lppd; pareto_k_counts (k <= 0.5, (0.5, 0.7],
+        (0.7, 1], > 1), n_p_waic_large (p_waic > 0.4), count -- pooled over the states and per state under `<key>_per_state`.
+        NaN where nothing was scored: nothing raises."""
+        col = {name: i for i, name in enumerate(LOO_COLUMNS)}
+
+        def scores(r):
+            c = r[..., col["count"]]
+            some = c > 0
+            cs = np.where(some, c, 1.0)
+            nan = np.full(r.shape[:-1], np.nan)
+            pick = lambda name: np.where(some, r[..., col[name]], nan)                                         # noqa: E731
+
+            def se(s1, s2):
+                var = np.maximum(r[..., col[s2]] / cs - (r[..., col[s1]] / cs) ** 2, 0.0)
+                return np.where(some, np.sqrt(cs * var), nan)
+            return {"elpd_loo": pick("sum_elpd_loo"), "se": se("sum_elpd_loo", "sum_elpd_loo_sq"), "p_loo": pick("sum_p_loo"),
+                    "looic": -2.0 * pick("sum_elpd_loo"), "elpd_waic": pick("sum_elpd_waic"),
+                    "se_waic": se("sum_elpd_waic", "sum_elpd_waic_sq"), "p_waic": pick("sum_p_waic"),
+                    "waic": -2.0 * pick("sum_elpd_waic"), "lppd": pick("sum_lppd"),
+                    "pareto_k_counts": r[..., col["k_good"]:col["k_very_bad"] + 1], "n_p_waic_large": r[..., col["p_waic_large"]],
+                    "count": c}
+        pooled, per = scores(self.table.sum(0)), scores(self.table)
+        out = {k: (v if v.ndim else float(v)) for k, v in pooled.items()}
+        out.update({f"{k}_per_state": v for k, v in per.items()})
+        return out
+
+
+def compare(results: Dict[str, Union["LooResult", "PredictiveSummary"]], ic: str = "loo") -> List[Dict[str, object]]:
+    """Rank fitted models by expected log pointwise predictive density on the SAME data (what arviz.compare reports).  results:
+    name -> LooResult (or a PredictiveSummary made with loo=True); ic: "loo" or "waic".  Returns one row per model, best first:
+    {name, rank, elpd, se, p, elpd_diff (to the best, <= 0), dse (sqrt(n var) of the pointwise difference to the best over the n
+    entries scored in both, ddof 1; 0 for the best), weight (pseudo-BMA: the softmax of elpd), warning (a Pareto k > 0.7 for
+    "loo", a p_waic > 0.4 for "waic")}.  Raises when the models were not scored on the same entries."""
+    if ic not in ("loo", "waic"):
+        raise ValueError('ic must be "loo" or "waic"')
+    if not results:
+        raise ValueError("compare needs at least one result")
+    loos = {}
+    for name, r in results.items():
+        r = r.loo if isinstance(r, PredictiveSummary) else r
+        if not isinstance(r, LooResult):
+            raise ValueError(f"{name!r} carries no LooResult (was its summary made with loo=True?)")
+        loos[name] = r
+    point = {name: torch.as_tensor(r.elpd_loo if ic == "loo" else r.elpd_waic).to(torch.float64) for name, r in loos.items()}
+    first = next(iter(point))
+    scored = ~torch.isnan(point[first])
+    for name, v in point.items():
+        if v.shape != point[first].shape or not torch.equal(~torch.isnan(v.to(scored.device)), scored):
+            raise ValueError(f"{name!r} and {first!r} were not scored on the same entries: the comparison needs the same data")
+    rows = []
+    for name, r in loos.items():
+        e = r.estimates()
+        warn = bool(e["pareto_k_counts"][2:].sum() > 0) if ic == "loo" else bool(e["n_p_waic_large"] > 0)
+        rows.append({"name": name, "elpd": e["elpd_loo" if ic == "loo" else "elpd_waic"], "se": e["se" if ic == "loo" else "se_waic"],
+                     "p": e["p_loo" if ic == "loo" else "p_waic"], "warning": warn})
+    rows.sort(key=lambda row: -row["elpd"] if row["elpd"] == row["elpd"] else float("inf"))
+    best = rows[0]
+    n = int(scored.sum())
+    el = np.array([row["elpd"] for row in rows])
+    with np.errstate(invalid="ignore"):
+        w = np.exp(el - np.nanmax(el)) if n else np.full(len(rows), np.nan)
+    w = w / w.sum()
+    for rank, (row, wt) in enumerate(zip(rows, w)):
+        d = (point[row["name"]].to(scored.device) - point[best["name"]].to(scored.device))[scored]
+        row["rank"], row["weight"] = rank, float(wt)
+        row["elpd_diff"] = float(row["elpd"] - best["elpd"])
+        row["dse"] = float(torch.sqrt(n * d.var(unbiased=True))) if n > 1 and rank > 0 else (0.0 if rank == 0 else float("nan"))
+    return rows
 
 
 def band_metrics(band_table: np.ndarray) -> Dict[str, Union[float, np.ndarray]]:
@@ -188,10 +292,14 @@ class PredictiveAccumulator:
 
     quantiles (keyword, fractions in (0, 1)) with expected_draws (the most draws that will be folded): `fold` also keeps the
     tail_size(quantiles, expected_draws) smallest and largest values of every entry (hode.capi.pred_tails) and `finish` turns
-    them into the exact quantiles of the folded draws; like the rest of the state they do not depend on how the draws were cut."""
+    them into the exact quantiles of the folded draws; like the rest of the state they do not depend on how the draws were cut.
+
+    loo=True (keyword; needs observations and, in every `fold`, sigma; the same expected_draws): `fold` also folds the pointwise
+    log likelihood (hode.capi.pred_loo_fold, loo_tail_size(expected_draws, r_eff) ratios kept per entry) and `finish` returns
+    PSIS-LOO and WAIC as `PredictiveSummary.loo`.  r_eff: the relative efficiency of the draws (1 for independent draws)."""
 
     def __init__(self, n_traj: int, T: int, observations=None, observation_mask=None, dtype=torch.float32, *, quantiles=None,
-                 expected_draws: Optional[int] = None):
+                 expected_draws: Optional[int] = None, loo: bool = False, r_eff: float = 1.0):
         if dtype not in (torch.float32, torch.float64):
             raise ValueError("dtype must be torch.float32 or torch.float64")
         if n_traj < 1 or T < 1:
@@ -223,6 +331,14 @@ class PredictiveAccumulator:
             self.expected_draws = int(expected_draws)
             self.tail_state = hode.capi.pred_tail_state(self.N, tail_size(self.levels, self.expected_draws), dtype, dev)
         self._tail_version = 0
+        self.loo_state, self.r_eff = None, float(r_eff)
+        if loo:
+            if self.obs is None:
+                raise ValueError("loo needs observations: the likelihood of nothing is undefined")
+            if expected_draws is None or int(expected_draws) < 1:
+                raise ValueError("loo needs expected_draws >= 1: the number of draws that will be folded sizes the buffer")
+            self.expected_draws = int(expected_draws)
+            self.loo_state = hode.capi.pred_loo_state(self.N, loo_tail_size(self.expected_draws, self.r_eff), dev)
 
     @classmethod
     def from_moments(cls, predictions, uncertainties, observations, observation_mask=None, dtype=None):
@@ -270,6 +386,8 @@ class PredictiveAccumulator:
         if y.dtype != self.dtype:
             y = y.to(self.dtype)
         sig = self._sigma(sigma, S)
+        if self.loo_state is not None and sig is None:
+            raise ValueError("loo needs sigma in every fold: without observation noise there is no likelihood")
         if status is not None:
             status = torch.as_tensor(status).reshape(S, self.n_traj)
         y = y.reshape(S, self.N) if y.is_contiguous() else y
@@ -277,6 +395,8 @@ class PredictiveAccumulator:
         if self.tail_state is not None:
             hode.capi.pred_tails(y, self.tail_state, status)
             self._tail_version += 1
+        if self.loo_state is not None:
+            hode.capi.pred_loo_fold(y, self.loo_state, self.obs, self.mask, sig, status)
         if sig is not None:
             self._var_sum += (sig * sig).sum(0)
         self.n_folded += S
@@ -286,6 +406,8 @@ class PredictiveAccumulator:
         if not 1 <= int(n_bins) <= hode.capi.PRED_MAX_BINS:
             raise ValueError(f"n_bins must lie in 1..{hode.capi.PRED_MAX_BINS}")
         thr = half_normal_thresholds(int(n_bins))
+        if self.loo_state is not None and self.n_folded > self.expected_draws:
+            raise ValueError(f"{self.n_folded} draws were folded but the LOO buffer was sized for expected_draws = {self.expected_draws}")
         extra = (self._var_sum / max(self.n_folded, 1)).tolist()
         mean, sd, pit, table = hode.capi.pred_score(self.state, self.dtype, self.obs, self.mask, extra, thr)
         shape = (self.n_traj, self.T, 6)
@@ -298,6 +420,9 @@ class PredictiveAccumulator:
             q, bt = hode.capi.pred_quantiles(self.tail_state, self.levels, self.obs if band else None, self.mask if band else None, band)
             extra = dict(levels=self.levels, quantiles=q.view(len(self.levels), *shape), band_table=None if bt is None else bt.cpu().numpy(),
                          tails=self._tails_reader())
+        if self.loo_state is not None:
+            out, lt = hode.capi.pred_loo_finish(self.loo_state, self.dtype, self.r_eff)
+            extra["loo"] = LooResult(*[out[k].view(shape) for k in hode.capi.PRED_LOO_OUTPUTS], lt.cpu().numpy(), self.r_eff)
         return PredictiveSummary(mean.view(shape), sd.view(shape), pit.view(shape), self.state["n"].view(shape).clone(),
                                  table.cpu().numpy(), thr, **extra)
 
@@ -325,7 +450,7 @@ def _rep_inputs(S, x0, t_span, external_inputs):
 
 def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None, n_bins: int = 10,
                        max_bytes: int = _DEFAULT_MAX_BYTES, solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8,
-                       dtype=torch.float32, *, quantiles=None) -> PredictiveSummary:
+                       dtype=torch.float32, *, quantiles=None, loo: bool = False, r_eff: float = 1.0) -> PredictiveSummary:
     """The posterior-predictive summary of `draws` on `batch` {initial_state, time_points[, observations, observation_mask,
     external_inputs]}.  draws: a list of named parameter overrides (what `variational_params.sample` and `forward_param_sets`
     take), or a pair (nn_flat [S, P], ode_vec [S, 17]) of parameter tensors.  sigma: the observation noise, None, a scalar, six
@@ -333,7 +458,10 @@ def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None,
     is ONE batched solve (no tape) and is folded with the solve's statuses before the next one starts: no more than one
     piece of trajectories exists at a time, and the result does not depend on the cut.  quantiles (fractions in (0, 1), e.g.
     (0.025, 0.975) for the 95 % credible band): also the exact empirical quantiles of the LATENT trajectories across the draws,
-    `PredictiveSummary.quantiles` / `.band()`; sigma does not enter them."""
+    `PredictiveSummary.quantiles` / `.band()`; sigma does not enter them.  loo=True (needs observations and sigma): also PSIS-LOO
+    and WAIC of the pointwise log likelihood, `PredictiveSummary.loo`, with the relative efficiency r_eff of the draws."""
+    if loo and sigma is None:
+        raise ValueError("loo needs sigma: without observation noise there is no likelihood")
     from models.hybrid_ode_nn import _compute_device
     dev = _compute_device()
     x0 = batch["initial_state"]
@@ -344,7 +472,7 @@ def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None,
     named = not (isinstance(draws, tuple) and len(draws) == 2 and isinstance(draws[0], torch.Tensor))
     S = len(draws) if named else draws[0].shape[0]
     acc = PredictiveAccumulator(B, T, batch.get("observations"), batch.get("observation_mask"), dtype, quantiles=quantiles,
-                                expected_draws=None if quantiles is None else max(S, 1))
+                                expected_draws=None if quantiles is None and not loo else max(S, 1), loo=loo, r_eff=r_eff)
     sig = acc._sigma(sigma, S)
     for lo, hi in cut_draws(S, B * T * 6 * 4, max_bytes):                         # (the solve's trajectories are fp32)
         n = hi - lo

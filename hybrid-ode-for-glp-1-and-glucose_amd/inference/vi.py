@@ -132,19 +132,21 @@ class VariationalInference:
         return preds.mean(dim=0), preds.std(dim=0)
 
     def predictive_summary(self, batch: Dict[str, torch.Tensor], n_samples: int = 100, noise_sigma=None, n_bins: int = 10,
-                           max_bytes: Optional[int] = None, *, quantiles=None):
+                           max_bytes: Optional[int] = None, *, quantiles=None, loo: bool = False, r_eff: float = 1.0):
         """`posterior_predictive` without the stack of draws, and scored: the n_samples draws -- one `sample(1)` at a time, the
         same RNG consumption -- are solved a piece at a time under max_bytes of trajectories and folded into a
         `PredictiveSummary` (inference/predictive.py): mean / std / PIT per entry and, against batch["observations"], the
         scores of its `metrics()`.  noise_sigma (None, a scalar or one value per state) is the observation noise of the
         predictive; None scores the draws' own spread, as the reference's evaluate_model does.  quantiles (fractions in (0, 1),
         e.g. (0.025, 0.975)): also the exact quantiles of the latent trajectories across the draws, the credible band of the
-        reference's third figure (`PredictiveSummary.quantiles`, `.band()`)."""
+        reference's third figure (`PredictiveSummary.quantiles`, `.band()`).  loo=True (needs noise_sigma): also PSIS-LOO and WAIC,
+        `PredictiveSummary.loo`, for `inference.compare`."""
         from inference import predictive as PR
         with torch.no_grad():
             draws = [self.variational_params.sample(1)[0] for _ in range(n_samples)]
         return PR.predictive_summary(self.model, draws, batch, sigma=noise_sigma, n_bins=n_bins,
-                                     max_bytes=PR._DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, quantiles=quantiles)
+                                     max_bytes=PR._DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, quantiles=quantiles, loo=loo,
+                                     r_eff=r_eff)
 
     # ------------------------------------------------------------------ checkpoints
     def save_checkpoint(self, path: str):

@@ -644,6 +644,82 @@ int hode_pred_quantiles_f32(void *stream, int64_t N, int K, const int32_t *cnt, 
 int hode_pred_quantiles_f64(void *stream, int64_t N, int K, const int32_t *cnt, double *lo, double *hi, int n_levels, const double *levels,
                             double *out, const double *obs, const uint8_t *mask, double *band_table, double *work);
 
+/* =====================================================================================================
+ * Model comparison: PSIS-LOO and WAIC folded across the draws (inference/predictive.py `loo=`, inference.compare): what
+ * arviz.loo / arviz.waic / arviz.compare compute from the [draws][N] block of pointwise log likelihoods, without the block
+ * (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao & Gabry 2024; Zhang & Stephens 2009).
+ *
+ * For an OBSERVED entry i (obs, mask as above; N % 6 == 0, the state of entry i is i % 6) and a draw s that pred_fold would
+ * take (status zero, y finite) with sigma[s][k] > 0, the pointwise log likelihood is pred_fold's lp,
+ *   z = (obs - y) / sigma;  l = -z^2 / 2 - log sigma - log(2 pi) / 2,
+ * and r = -l is the log importance ratio of leaving the observation out.  Pareto smoothing needs the M + 1 largest r of an
+ * entry and sums over the rest, M = ceil(min(n / 5, 3 sqrt(n / r_eff))).
+ *
+ * The LOO state of the entries, DEVICE memory the caller owns:
+ *   cnt          int32[N]      draws that produced an l
+ *   lmean, lm2   double[N]     Welford's mean and sum of squared deviations of l (WAIC)
+ *   pmax, psum   double[N]     streaming log-sum-exp of l: sum_s exp(l_s) = exp(pmax) psum (lppd; it does not read pred_fold's)
+ *   top          double[K][N]  the min(cnt, K) largest r, slot j of entry i at j * N + i (a binary min-heap: slot 0 is the least)
+ *   rmax, rsum   double[N]     streaming log-sum-exp of every r that is not in top
+ * A fresh state is all zero except pmax = rmax = -infinity; top needs no initialisation.
+ *
+ * hode_pred_loo_fold_* takes n_draws more draws y[n_draws][N], ONE AT A TIME IN DRAW ORDER, per entry:
+ *   d = l - lmean;  lmean += d / (cnt + 1);  lm2 += d * (l - lmean);
+ *   l > pmax ?  (psum = psum * exp(pmax - l) + 1, pmax = l)  :  psum += exp(l - pmax);
+ *   while cnt < K, r enters top; afterwards, when the least of top is < r, r replaces it and the replaced value is added to
+ *   {rmax, rsum} as l was to {pmax, psum}; otherwise r itself is added;  cnt += 1.
+ * Every r is therefore in exactly one of top and {rmax, rsum}: no subtraction forms the sum of the non-tail ratios.  All of
+ * it is fp64 without contraction and a draw is a pure update of the state in memory: any split of the draws into consecutive
+ * calls leaves bit-identical state; a permutation of the draws leaves the same multiset in top and the four running sums equal
+ * to rounding.  A lane owns one entry (no reduction, no atomics).  K is a run-time argument without a cap.
+ * HODE_EINVAL: n_draws < 0, N < 6 or N % 6 != 0, K < 2, a NULL state pointer, obs or sigma NULL (without observation noise
+ * there is no likelihood; hence a mask without obs is refused too), y NULL with n_draws > 0, with status a row_len that is no
+ * multiple of 6 or does not divide N.  n_draws == 0 is a no-op without a launch.
+ *
+ * hode_pred_loo_finish_* reads a state and writes, per entry in the working precision R, elpd_loo, pareto_k, elpd_waic, p_waic
+ * and lppd.  With n = cnt[i], h = min(n, K) and r_eff (a HOST scalar in (0, 1], the relative efficiency of the draws; 1 for
+ * independent draws), all five are NaN when n < 2 or M + 1 > h (the state was sized for fewer draws; unobserved entries
+ * have n = 0).  Otherwise:
+ *   shift     c = the largest r;  x = r - c;  x_cut = max(x of the (M + 1)-th largest, log(DBL_MIN));  e_cut = exp(x_cut)
+ *   tail      the held values with x > x_cut (strictly: ties with the cut are not tail), t of them, ascending, j = 1..t
+ *   fit       t <= 4: k = +infinity, nothing is smoothed.  Else on a_j = exp(x_j) - e_cut:
+ *               m = 30 + floor(sqrt(t));  b_q = (1 - sqrt(m / (q - 1/2))) / (3 a_[floor(t / 4 + 1/2)]) + 1 / a_t,  q = 1..m
+ *               k_q = mean_j log1p(-b_q a_j);  L_q = t (log(-b_q / k_q) - k_q - 1);  w_q = 1 / sum_p exp(L_p - L_q)
+ *               b = sum w_q b_q / sum w_q over the q with w_q >= 10 * 2^-52
+ *               k = mean_j log1p(-b a_j);  sigma = -k / b;  k <- (t k + 5) / (t + 10)
+ *   smooth    when k is finite and sigma > 0, the j-th smallest tail value becomes
+ *               x~_j = min(log(a~_j + e_cut), 0),  a~_j = sigma expm1(-k log1p(-p_j)) / k  (-sigma log1p(-p_j) when |k| < 2^-52),
+ *               p_j = (j - 1/2) / t;  otherwise x~_j = x_j
+ *   estimate  elpd_loo = LSE({log(n - t) - c} u {x~_j - r_j}) - LSE({rmax + log rsum - c} u {x of the held non-tail values} u {x~_j})
+ *             (in log space: (n - t) exp(-c) underflows for heavy tails);  pareto_k = k
+ *   lppd = pmax + log(psum / n);  p_waic = lm2 / (n - 1);  elpd_waic = lppd - p_waic
+ * The call SORTS top in place (ascending; a sorted buffer is still a valid heap, so folding may go on afterwards: that is
+ * why top is not const here).
+ * fit: DEVICE double[rows][N], scratch space, rows = (K - 1) + 30 + floor(sqrt(K - 1)): the a_j / x~_j and the L_q of every
+ * entry, slot-major like top.
+ * table: DEVICE double[6][HODE_PRED_LOO_COLS], per-state sums over the scored entries (those whose outputs are not NaN by the
+ * rule above), from the fp64 values before they are rounded to R, with p_loo = lppd - elpd_loo:
+ *   0 count   1 sum elpd_loo   2 sum elpd_loo^2   3 sum p_loo   4 sum elpd_waic   5 sum elpd_waic^2   6 sum p_waic   7 sum lppd
+ *   8..11 counts of k <= 0.5, 0.5 < k <= 0.7, 0.7 < k <= 1, k > 1 (+infinity included)   12 count of p_waic > 0.4
+ * reduced in the fixed order of hode_pred_score_* (work: DEVICE double[HODE_PRED_SCORE_BLOCKS * 6 * HODE_PRED_LOO_COLS],
+ * scratch space): the same call gives the same bits.
+ * HODE_EINVAL: N < 6 or N % 6 != 0, K < 2, r_eff outside (0, 1] or NaN, a NULL among the state, the outputs, table, fit
+ * and work.
+ * ===================================================================================================== */
+#define HODE_PRED_LOO_COLS 13
+int hode_pred_loo_fold_f32(void *stream, int n_draws, int64_t N, const float *y, const float *obs, const uint8_t *mask, const double *sigma,
+                           const int32_t *status, int64_t row_len, int K, int32_t *cnt, double *lmean, double *lm2, double *pmax,
+                           double *psum, double *top, double *rmax, double *rsum);
+int hode_pred_loo_fold_f64(void *stream, int n_draws, int64_t N, const double *y, const double *obs, const uint8_t *mask, const double *sigma,
+                           const int32_t *status, int64_t row_len, int K, int32_t *cnt, double *lmean, double *lm2, double *pmax,
+                           double *psum, double *top, double *rmax, double *rsum);
+int hode_pred_loo_finish_f32(void *stream, int64_t N, int K, double r_eff, const int32_t *cnt, const double *lmean, const double *lm2,
+                             const double *pmax, const double *psum, double *top, const double *rmax, const double *rsum, float *elpd_loo,
+                             float *pareto_k, float *elpd_waic, float *p_waic, float *lppd, double *table, double *fit, double *work);
+int hode_pred_loo_finish_f64(void *stream, int64_t N, int K, double r_eff, const int32_t *cnt, const double *lmean, const double *lm2,
+                             const double *pmax, const double *psum, double *top, const double *rmax, const double *rsum, double *elpd_loo,
+                             double *pareto_k, double *elpd_waic, double *p_waic, double *lppd, double *table, double *fit, double *work);
+
 #ifdef __cplusplus
 }
 #endif
