@@ -1,11 +1,13 @@
 // hode_solve_jvp.hip -- K6: tangent-linear (forward-mode) pass over the tape of the forward solve.
 //
-// No reference counterpart.  For K tangent directions per trajectory it computes
+// The reference has no sensitivities; the CPU restatement is hode_oracle_solve_jvp (oracle/hode_oracle_impl.h).  For K tangent
+// directions per trajectory it computes
 //     dy[b, k] = (d y_b / d ode_p) v_ode[set(b), k] + (d y_b / d x0_b) v_x0[b, k]
 // as the exact derivative of the discrete scheme the forward ran: the taped accepted steps, their step sizes held constant,
 // the same tableau and grid breaks.  It walks the tape FORWARD, as the adjoint (hode_solve_bwd.hip) walks it backward, and
 // differentiates the same thing: the two are transposes of each other, so <gy, J v> = <J^T gy, v> to rounding.
-// CPU restatement of the adjoint it is the transpose of: oracle/hode_oracle_impl.h (hode_oracle_solve_bwd).
+// hode_oracle_solve_jvp walks the same tape with Jacobians taken from the oracle's rhs_vjp_one (not from the coefficient table
+// below); tests/test_jvp_enum_gpu.py holds every instantiation of this kernel to it, column by column (tests/_jvp_cases.py).
 //
 // Mapping: one trajectory per wavefront, one hidden unit per lane (hode_xlane.h), K_TILE directions per wave.
 //   * the hidden matrices are loaded into VGPRs once per wave in the forward's register order (mlp_load), so a layer of the

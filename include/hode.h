@@ -193,7 +193,8 @@ int hode_solve_bwd_inputs_f64(void *stream, int B, int T, const double *t, int t
                               const int32_t *status, void *tape, const double *gy, double *gx0,
                               double *gnn, double *gode, double *gmeal, double *gtvns, double *ggd);
 /* ---- K6: tangent-linear (forward-mode) solve over the tape of the forward -- the sensitivities of a trajectory with respect to
- *      a few directions (no reference counterpart: the reference has no sensitivities; per-patient calibration needs them).
+ *      a few directions (the reference has no sensitivities; per-patient calibration needs them.  CPU restatement:
+ *      hode_oracle_solve_jvp_f32 / _f64, oracle/hode_oracle_impl.h, to which tests/test_jvp_enum_gpu.py holds this kernel).
  *      For K directions per trajectory
  *        dy[b,k,:,:] = (d y_b / d ode_p) v_ode[set(b),k,:] + (d y_b / d x0_b) v_x0[b,k,:]
  *      v_ode [n_sets][K][17] and v_x0 [B][K][6]: either may be NULL (that part is 0), not both; dy [B][K][T][6] is WRITTEN.

@@ -10,6 +10,8 @@
  * generated in the build container by importing the reference itself
  * (tools/capture_golden.py writes tests/golden/ .npz files).  The input gradients (d/d{meal, tVNS, GD} of the RHS and of the
  * solve, the *_inputs_* entry points) are pinned to reference autograd (fixture G10) in tests/test_input_grads_oracle.py.
+ * The tangent-linear solve (hode_oracle_solve_jvp_*) takes its Jacobians from rhs_vjp_one and is pinned by duality with the adjoint
+ * and by finite differences in tests/test_jvp_oracle.py.
  *
  * Third-party arithmetic restated here: scipy.integrate.solve_ivp(method='RK45'), SciPy 1.15.3
  * (reference requirements.txt:3 says scipy>=1.10.0, unpinned; 1.15.3 is what the reference

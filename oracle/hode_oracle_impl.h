@@ -603,3 +603,125 @@ int SFX(hode_oracle_solve_bwd)(int B, int T, const REAL *tg, int t_batched, cons
     return SFX(hode_oracle_solve_bwd_inputs)(B, T, tg, t_batched, meal, meal_mode, tvns, tvns_mode, gd, gd_mode, ode, nn_p, H, L,
                                              method, max_steps, nsteps, status, tape_v, gy, gx0, gnn, gode, NULL, NULL, NULL);
 }
+
+/*
+ * Tangent-linear ("forward-mode") pass over the same tape: the restatement of hode_solve_jvp_* (include/hode.h, K6).
+ *   dy[b,k,:,:] = (d y_b / d ode) v_ode[k,:] + (d y_b / d x0_b) v_x0[b,k,:]      v_ode [K][17], v_x0 [B][K][6] (either may be
+ *   NULL = that part is 0, not both), dy [B][K][T][6] is written.  One parameter set per call.
+ * No second hand-derived tangent of the RHS: at every taped stage the stage state is recomputed as the adjoint above does, and
+ * the rows of df/dx (6x6) and df/dtheta (6x17) come from six calls of rhs_vjp_one with the unit cotangents (that function is
+ * pinned to reference autograd by fixtures G7 / G10).  Then dK_s = J_x (dy + h sum_j a_sj dK_j) + J_theta v and
+ * dy += h sum_s b_s dK_s, step sizes held constant.  All arithmetic in REAL.
+ * Rows follow y: row 0 (and the rows of the same time behind it) = v_x0; a row is written when a step with HODE_SEG_CLOSED
+ * closes its interval; a repeated time copies the row before it; after the last taped step of a failed trajectory every later
+ * row is 0.
+ */
+int SFX(hode_oracle_solve_jvp)(int B, int T, const REAL *tg, int t_batched, const REAL *meal,
+                               int meal_mode, const REAL *tvns, int tvns_mode, const REAL *gd,
+                               int gd_mode, const REAL *ode, const REAL *nn_p, int H, int L,
+                               int method, int max_steps, const int *nsteps, const int *status, const void *tape_v,
+                               int K, const REAL *v_ode, const REAL *v_x0, REAL *dy)
+{
+    (void)status;                                  /* the tape says where a failed trajectory stopped */
+    SFX(mlp_t) m;
+    if (SFX(mlp_bind)(&m, nn_p, H, L) < 0) return -1;
+    if (T < 1 || B < 0 || K < 1 || (!v_ode && !v_x0)) return -1;
+    const SFX(tape_t) *tape = (const SFX(tape_t) *)tape_v;
+    REAL *cur = (REAL *)malloc(sizeof(REAL) * 6 * (size_t)K);
+    if (!cur) return -1;
+    REAL act[HODE_MAXL + 1][HODE_MAXH];
+    int S;
+    double Aloc[6][6] = {{0}}, bw[6] = {0}, cw[6] = {0};
+    if (method == 1) {
+        S = 4;
+        Aloc[1][0] = 0.5; Aloc[2][1] = 0.5; Aloc[3][2] = 1.0;
+        bw[0] = 1.0 / 6; bw[1] = 2.0 / 6; bw[2] = 2.0 / 6; bw[3] = 1.0 / 6;
+        cw[0] = 0; cw[1] = 0.5; cw[2] = 0.5; cw[3] = 1.0;
+    } else {
+        S = 6;
+        for (int i = 0; i < 6; ++i) { for (int j = 0; j < i; ++j) Aloc[i][j] = SFX(dpA)[i][j]; bw[i] = SFX(dpA)[6][i]; cw[i] = SFX(dpC)[i]; }
+    }
+    for (int b = 0; b < B; ++b) {
+        const REAL *tb = t_batched ? tg + (size_t)b * T : tg;
+        REAL *out = dy + (size_t)b * K * T * 6;
+        const int n = nsteps[b] < max_steps ? nsteps[b] : max_steps;
+        for (int k = 0; k < K; ++k)
+            for (int i = 0; i < 6; ++i) {
+                cur[6 * k + i] = v_x0 ? v_x0[((size_t)b * K + k) * 6 + i] : (REAL)0;
+                out[((size_t)k * T + 0) * 6 + i] = cur[6 * k + i];
+            }
+        int st = 0, r = 1;
+        for (int kiv = 0; kiv + 1 < T; ++kiv) {
+            if (tb[kiv + 1] > tb[kiv]) {
+                int closed = 0;
+                while (st < n && (tape[(size_t)b * max_steps + st].seg & (HODE_SEG_CLOSED - 1)) == kiv) {
+                    const SFX(tape_t) *e = tape + (size_t)b * max_steps + st;
+                    closed = (e->seg & HODE_SEG_CLOSED) != 0;
+                    SFX(seg_t) s;
+                    s.t0 = tb[kiv]; s.t1 = tb[kiv + 1];
+                    s.m0 = SFX(inp_at)(meal, meal_mode, b, T, kiv); s.m1 = SFX(inp_at)(meal, meal_mode, b, T, kiv + 1);
+                    s.v0 = SFX(inp_at)(tvns, tvns_mode, b, T, kiv); s.v1 = SFX(inp_at)(tvns, tvns_mode, b, T, kiv + 1);
+                    s.d0 = SFX(inp_at)(gd, gd_mode, b, T, kiv); s.d1 = SFX(inp_at)(gd, gd_mode, b, T, kiv + 1);
+                    s.use_gd = (gd != NULL && gd_mode != 0);
+                    const REAL h = e->h, tc = e->t;
+                    REAL mm, vv, dd;
+                    REAL Y[6][6], Kk[6][6], JX[6][6][6], JT[6][6][17];
+                    /* recompute the stages (as the adjoint does) and take the Jacobian rows at each */
+                    for (int sI = 0; sI < S; ++sI) {
+                        for (int i = 0; i < 6; ++i) {
+                            REAL acc = 0;
+                            for (int j = 0; j < sI; ++j) acc += (REAL)Aloc[sI][j] * Kk[j][i];
+                            Y[sI][i] = e->y[i] + h * acc;
+                        }
+                        REAL ts = tc + (REAL)cw[sI] * h;
+                        if (method != 1 && sI == 0) ts = tc;
+                        SFX(seg_eval)(&s, ts, &mm, &vv, &dd);
+                        SFX(rhs_one)(&m, ode, ts, Y[sI], mm, vv, dd, s.use_gd, Kk[sI], act);
+                        for (int i = 0; i < 6; ++i) {
+                            REAL unit[6] = {0, 0, 0, 0, 0, 0}, gx[6] = {0, 0, 0, 0, 0, 0};
+                            ACC go[17] = {0};
+                            unit[i] = (REAL)1;
+                            SFX(rhs_vjp_one)(&m, ode, ts, Y[sI], mm, vv, dd, s.use_gd, unit, gx, NULL, go, (REAL)1, NULL);
+                            for (int c = 0; c < 6; ++c) JX[sI][i][c] = gx[c];
+                            for (int p = 0; p < 17; ++p) JT[sI][i][p] = (REAL)go[p];
+                        }
+                    }
+                    for (int k = 0; k < K; ++k) {
+                        REAL *d = cur + 6 * k;
+                        const REAL *v = v_ode ? v_ode + (size_t)k * 17 : NULL;
+                        REAL dK[6][6];
+                        for (int sI = 0; sI < S; ++sI) {
+                            REAL dY[6];
+                            for (int i = 0; i < 6; ++i) {
+                                REAL acc = 0;
+                                for (int j = 0; j < sI; ++j) acc += (REAL)Aloc[sI][j] * dK[j][i];
+                                dY[i] = d[i] + h * acc;
+                            }
+                            for (int i = 0; i < 6; ++i) {
+                                REAL acc = 0;
+                                for (int c = 0; c < 6; ++c) acc += JX[sI][i][c] * dY[c];
+                                if (v) for (int p = 0; p < 17; ++p) acc += JT[sI][i][p] * v[p];
+                                dK[sI][i] = acc;
+                            }
+                        }
+                        for (int i = 0; i < 6; ++i) {
+                            REAL acc = 0;
+                            for (int sI = 0; sI < S; ++sI) acc += (REAL)bw[sI] * dK[sI][i];
+                            d[i] = d[i] + h * acc;
+                        }
+                    }
+                    ++st;
+                }
+                if (!closed) break;                /* no taped step closes this interval: the trajectory failed here */
+            }
+            for (int k = 0; k < K; ++k)
+                for (int i = 0; i < 6; ++i) out[((size_t)k * T + r) * 6 + i] = cur[6 * k + i];
+            ++r;
+        }
+        for (; r < T; ++r)
+            for (int k = 0; k < K; ++k)
+                for (int i = 0; i < 6; ++i) out[((size_t)k * T + r) * 6 + i] = (REAL)0;
+    }
+    free(cur);
+    return 0;
+}

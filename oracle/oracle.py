@@ -207,6 +207,26 @@ def solve_bwd_inputs(sol, gy, want_gnn=True, want_gode=True, want_inputs=INPUT_K
     return gx0, gnn, gode, gin
 
 
+def solve_jvp(sol, v_ode=None, v_x0=None):
+    """Tangent-linear pass over the tape of `sol` (want_tape=True): v_ode [K,17] and / or v_x0 [B,K,6] -> dy [B,K,T,6], the
+    restatement of hode.solve_jvp for ONE parameter set.  The Jacobians come from rhs_vjp_one with unit cotangents."""
+    t, t_batched, meal, tvns, gd, ode, nn_p, H, L, method, dtype = sol.args
+    assert sol.tape is not None and (v_ode is not None or v_x0 is not None)
+    B, T = sol.y.shape[:2]
+    v_ode, v_x0 = _arr(v_ode, dtype), _arr(v_x0, dtype)
+    K = v_ode.shape[0] if v_ode is not None else v_x0.shape[1]
+    assert v_ode is None or v_ode.shape == (K, 17), v_ode.shape
+    assert v_x0 is None or v_x0.shape == (B, K, 6), v_x0.shape
+    dy = np.full((B, K, T, 6), np.nan, dtype)
+    rc = getattr(lib(), f"hode_oracle_solve_jvp_{_sfx(dtype)}")(
+        C.c_int(B), C.c_int(T), _p(t), C.c_int(t_batched),
+        _p(meal), C.c_int(_mode(meal, B, T)), _p(tvns), C.c_int(_mode(tvns, B, T)),
+        _p(gd), C.c_int(_mode(gd, B, T)), _p(ode), _p(nn_p), C.c_int(H), C.c_int(L), C.c_int(method),
+        C.c_int(sol.max_steps), _p(sol.nsteps), _p(sol.status), _p(sol.tape), C.c_int(K), _p(v_ode), _p(v_x0), _p(dy))
+    assert rc == 0
+    return dy
+
+
 def solve_reference_mode(x0, t, meal, tvns, gd, ode, nn_p, H, L, rtol=1e-6, atol=1e-8):
     """What HybridODENN.forward(solver='rk45') computes (SciPy RK45 + dense output, fp32 RHS)."""
     x0 = _arr(x0, np.float32)
