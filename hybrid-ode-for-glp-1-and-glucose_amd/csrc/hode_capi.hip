@@ -106,7 +106,8 @@ int solve_bwd(void *stream, int B, int T, const R *t, int t_batched, const R *me
 }
 
 // tangent-linear solve (hode_solve_jvp_*): host checks first -- directions, modes, shapes -- then one launch
-template <typename R>
+// ANY (hode_solve_jvp_any_*): every shape the forward can tape; otherwise the tuned shapes only, the documented envelope of K6
+template <typename R, bool ANY = false>
 int solve_jvp(void *stream, int B, int T, const R *t, int t_batched, const R *meal, int meal_mode, const R *tvns, int tvns_mode,
               const R *gd, int gd_mode, const R *ode_p, const R *nn_p, int n_sets, int H, int L, int method, int max_steps,
               const int32_t *nsteps, const int32_t *status, const void *tape, int K, const R *v_ode, const R *v_x0, R *dy)
@@ -118,7 +119,8 @@ int solve_jvp(void *stream, int B, int T, const R *t, int t_batched, const R *me
     if (n_sets < 1 || (B % n_sets) != 0 || max_steps < 1) return HODE_EINVAL;
     if (method != HODE_METHOD_DP54 && method != HODE_METHOD_RK4) return HODE_EINVAL;
     // tuned shapes only (H <= 64, L <= 4, ReLU, one network per parameter set): the physics-on configurations
-    if (H < 1 || layers_of(L) < 1 || (L >> 16) != 0 || !tuned_shape(H, L)) return HODE_EUNSUPPORTED;
+    if (H < 1 || layers_of(L) < 1 || (L >> 16) != 0 || (!ANY && !tuned_shape(H, L))) return HODE_EUNSUPPORTED;
+    if (H > HODE_MAX_HIDDEN || layers_of(L) > HODE_MAX_LAYERS || act_of(L) > HODE_ACT_LEAKY_RELU) return HODE_EUNSUPPORTED;
     JvpArgs<R> a;
     a.B = B; a.T = T; a.t_batched = t_batched ? 1 : 0; a.gd_mode = gd_mode;
     a.n_sets = n_sets; a.H = H; a.P = nn_param_count(H, L); a.max_steps = max_steps; a.K = K;
@@ -128,6 +130,7 @@ int solve_jvp(void *stream, int B, int T, const R *t, int t_batched, const R *me
     a.tape_seg = (const int32_t *)((const char *)tape + tape_seg_offset(B, max_steps, sizeof(R)));
     a.tape_stage = (const R *)((const char *)tape + tape_stage_offset(B, max_steps, sizeof(R)));
     a.v_ode = v_ode; a.v_x0 = v_x0; a.dy = dy;
+    if (!tuned_shape(H, L)) return launch_solve_jvp_generic<R>((hipStream_t)stream, a, layers_of(L), act_of(L), method);
     return launch_solve_jvp<R>((hipStream_t)stream, a, layers_of(L), method);
 }
 
@@ -417,6 +420,23 @@ int hode_solve_jvp_f64(void *stream, int B, int T, const double *t, int t_batche
 {
     return solve_jvp<double>(stream, B, T, t, t_batched, meal, meal_mode, tvns, tvns_mode, gd, gd_mode, ode_p, nn_p,
                              n_sets, H, L, method, max_steps, nsteps, status, tape, K, v_ode, v_x0, dy);
+}
+
+int hode_solve_jvp_any_f32(void *stream, int B, int T, const float *t, int t_batched, const float *meal, int meal_mode,
+                           const float *tvns, int tvns_mode, const float *gd, int gd_mode, const float *ode_p,
+                           const float *nn_p, int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                           const int32_t *status, const void *tape, int K, const float *v_ode, const float *v_x0, float *dy)
+{
+    return solve_jvp<float, true>(stream, B, T, t, t_batched, meal, meal_mode, tvns, tvns_mode, gd, gd_mode, ode_p, nn_p,
+                                  n_sets, H, L, method, max_steps, nsteps, status, tape, K, v_ode, v_x0, dy);
+}
+int hode_solve_jvp_any_f64(void *stream, int B, int T, const double *t, int t_batched, const double *meal, int meal_mode,
+                           const double *tvns, int tvns_mode, const double *gd, int gd_mode, const double *ode_p,
+                           const double *nn_p, int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                           const int32_t *status, const void *tape, int K, const double *v_ode, const double *v_x0, double *dy)
+{
+    return solve_jvp<double, true>(stream, B, T, t, t_batched, meal, meal_mode, tvns, tvns_mode, gd, gd_mode, ode_p, nn_p,
+                                   n_sets, H, L, method, max_steps, nsteps, status, tape, K, v_ode, v_x0, dy);
 }
 
 int hode_adam_step_f32(void *stream, int64_t n, float *p, const float *g, float *m, float *v, float lr, float beta1,

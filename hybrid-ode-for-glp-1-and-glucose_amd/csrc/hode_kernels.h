@@ -80,6 +80,8 @@ int launch_solve_bwd_ws(hipStream_t s, const AdjArgs<float> &a, int L, int metho
 void launch_adj_reduce(hipStream_t s, const float *partials, int rowlen, int blocks_per_set, int n_sets, int P, float *gnn, float *gode);
 // tangent-linear solve (hode_solve_jvp.hip; tuned shapes, every dtype)
 template <typename R> int launch_solve_jvp(hipStream_t s, const JvpArgs<R> &a, int L, int method);
+// the same for generic networks (hode_generic_jvp.hip): one trajectory and a tile of directions per eight-wave team
+template <typename R> int launch_solve_jvp_generic(hipStream_t s, const JvpArgs<R> &a, int L, int act, int method);
 template <typename R> int launch_rhs_fwd(hipStream_t s, const RhsArgs<R> &a, int L);
 template <typename R> int launch_rhs_bwd(hipStream_t s, const RhsArgs<R> &a, int L);
 // generic network path (hode_generic.hip): H <= 128, L <= 8, weights streamed from L2

@@ -25,7 +25,7 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_solve_bwd_inputs_f32", "hode_solve_bwd_inputs_f64", "hode_rhs_bwd_inputs_f32", "hode_rhs_bwd_inputs_f64",
            "hode_mse_sets_f32", "hode_mse_sets_f64", "hode_hmc_refresh_f32", "hode_hmc_refresh_f64", "hode_hmc_leapfrog_f32",
            "hode_hmc_leapfrog_f64", "hode_hmc_accept_f32", "hode_hmc_accept_f64", "hode_hmc_welford_f32", "hode_hmc_welford_f64",
-           "hode_solve_jvp_f32", "hode_solve_jvp_f64",
+           "hode_solve_jvp_f32", "hode_solve_jvp_f64", "hode_solve_jvp_any_f32", "hode_solve_jvp_any_f64",
            "hode_nuts_begin_f32", "hode_nuts_begin_f64", "hode_nuts_pre_f32", "hode_nuts_pre_f64", "hode_nuts_post_f32",
            "hode_nuts_post_f64", "hode_nuts_compact", "hode_nuts_finish_f32", "hode_nuts_finish_f64",
            "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64", "hode_sobol_indices_f32", "hode_sobol_indices_f64",
@@ -263,7 +263,8 @@ def _solve_bwd(sol, gy, want_gnn, want_gode, want_inputs):
 
 
 def solve_jvp(sol, v_ode=None, v_x0=None):
-    """Tangent-linear pass over the tape of `sol` (made with want_tape=True; hode_solve_jvp_*, include/hode.h).
+    """Tangent-linear pass over the tape of `sol` (made with want_tape=True; hode_solve_jvp_any_*, include/hode.h: every network
+    solve_fwd can tape -- the tuned shapes through the kernel of hode_solve_jvp_*, every other through the generic one).
     v_ode [n_sets,K,17] (directions in the ODE constants of each parameter set) and/or v_x0 [B,K,6] (in the initial states).
     Returns dy[B,K,T,6] = (dy/d ode_p) v_ode + (dy/d x0) v_x0 -- the exact derivative of the discrete scheme the forward ran."""
     if sol.tape is None:
@@ -283,12 +284,12 @@ def solve_jvp(sol, v_ode=None, v_x0=None):
     if v_x0 is not None and tuple(v_x0.shape) != (B, K, 6):
         raise HodeError(f"v_x0 must be [B,K,6]=({B},K,6), got {tuple(v_x0.shape)}")
     dy = torch.empty(B, K, T, 6, dtype=dt, device=dev)
-    fn = getattr(load(), f"hode_solve_jvp_{_sfx(dt)}")
+    fn = getattr(load(), f"hode_solve_jvp_any_{_sfx(dt)}")
     _check(fn(_stream(), C.c_int(B), C.c_int(T), _ptr(t), C.c_int(t_batched),
               _ptr(meal), C.c_int(_mode(meal, B, T)), _ptr(tvns), C.c_int(_mode(tvns, B, T)),
               _ptr(gd), C.c_int(_mode(gd, B, T)), _ptr(ode_p), _ptr(nn_p), C.c_int(n_sets), C.c_int(H), C.c_int(L),
               C.c_int(method), C.c_int(sol.max_steps), _ptr(sol.nsteps), _ptr(sol.status), _ptr(sol.tape), C.c_int(K),
-              _ptr(v_ode), _ptr(v_x0), _ptr(dy)), "hode_solve_jvp")
+              _ptr(v_ode), _ptr(v_x0), _ptr(dy)), "hode_solve_jvp_any")
     return dy
 
 

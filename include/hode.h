@@ -224,6 +224,27 @@ int hode_solve_jvp_f64(void *stream, int B, int T, const double *t, int t_batche
                        int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
                        const int32_t *status, const void *tape, int K, const double *v_ode,
                        const double *v_x0, double *dy);
+/*      The same pass for EVERY network hode_solve_fwd_* can tape: argument list, semantics, rows and duality as above.
+ *      Envelope: 1 <= H <= HODE_MAX_HIDDEN (128), 1 <= L <= HODE_MAX_LAYERS (8), HODE_ACT_RELU / TANH / ELU / LEAKY_RELU in bits
+ *      8..15 of L, fp32 and fp64, both methods, every input mode, batched or shared grids, n_sets >= 1.  The tuned shapes take
+ *      the kernel of hode_solve_jvp_* (the same bits); every other shape takes a kernel of its own (hode_generic_jvp.hip: one
+ *      trajectory and a tile of directions per eight-wave team, act' from the taped post-activation values, no atomics), with
+ *      the same contracts: the same call gives the same bits, a K-direction call gives the bits of K one-direction calls, and a
+ *      trajectory's tangent does not depend on the rest of the batch.
+ *      HODE_EUNSUPPORTED for H > 128, L > 8, an unknown activation code and HODE_LAYERS_NN_SHARED; HODE_EINVAL as above, and a
+ *      bad argument outranks an unsupported shape -- all checked before any launch.                                          */
+int hode_solve_jvp_any_f32(void *stream, int B, int T, const float *t, int t_batched,
+                           const float *meal, int meal_mode, const float *tvns, int tvns_mode,
+                           const float *gd, int gd_mode, const float *ode_p, const float *nn_p,
+                           int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                           const int32_t *status, const void *tape, int K, const float *v_ode,
+                           const float *v_x0, float *dy);
+int hode_solve_jvp_any_f64(void *stream, int B, int T, const double *t, int t_batched,
+                           const double *meal, int meal_mode, const double *tvns, int tvns_mode,
+                           const double *gd, int gd_mode, const double *ode_p, const double *nn_p,
+                           int n_sets, int H, int L, int method, int max_steps, const int32_t *nsteps,
+                           const int32_t *status, const void *tape, int K, const double *v_ode,
+                           const double *v_x0, double *dy);
 int hode_rhs_bwd_inputs_f32(void *stream, int B, const float *x, const float *t, const float *meal,
                             const float *tvns, const float *gd, const float *ode_p, const float *nn_p,
                             int H, int L, const float *gout, float *gx, float *gt, float *gnn, float *gode,
