@@ -240,6 +240,31 @@ template <typename R> int hmc_welford(void *stream, int C, int D, int ld, int fl
     return launch_hmc_welford<R>((hipStream_t)stream, C, D, ld, flags, z, wf, minv);
 }
 
+// ---- population model (hode_population.hip)
+inline bool pop_ok(int A, int B, int K, int ld, uint32_t ode_mask)
+{
+    return A >= 0 && B >= 1 && K >= 1 && K <= 17 && !(ode_mask >> 17) && __builtin_popcount(ode_mask) == K && ld >= (int64_t)K * (B + 2) &&
+           (int64_t)A * ld <= ((int64_t)1 << 40) && (int64_t)A * B <= ((int64_t)1 << 36);
+}
+
+template <typename R> int pop_params(void *stream, int A, int B, int K, int ld, const R *coords, uint32_t ode_mask, const double *mu0,
+                                     const double *sd0, const double *tau0, double tau_log_sd, const R *ode_base, R *ode_p)
+{
+    if (!pop_ok(A, B, K, ld, ode_mask)) return HODE_EINVAL;
+    if (A == 0) return HODE_OK;
+    if (!coords || !mu0 || !sd0 || !tau0 || !ode_base || !ode_p) return HODE_EINVAL;
+    return launch_pop_params<R>((hipStream_t)stream, A, B, K, ld, coords, ode_mask, mu0, sd0, tau0, tau_log_sd, ode_base, ode_p);
+}
+
+template <typename R> int pop_grad(void *stream, int A, int B, int K, int ld, const R *coords, const R *gode, uint32_t ode_mask,
+                                   const double *sd0, const double *tau0, double tau_log_sd, R *glik)
+{
+    if (!pop_ok(A, B, K, ld, ode_mask)) return HODE_EINVAL;
+    if (A == 0) return HODE_OK;
+    if (!coords || !gode || !sd0 || !tau0 || !glik) return HODE_EINVAL;
+    return launch_pop_grad<R>((hipStream_t)stream, A, B, K, ld, coords, gode, ode_mask, sd0, tau0, tau_log_sd, glik);
+}
+
 // ---- No-U-Turn sampling (hode_nuts.hip)
 template <typename R> int nuts_begin(void *stream, int C, int D, int ld, const R *z, const R *p, const R *g, const double *U, const double *U0,
                                      const double *ke0, R *tree, double *dst, int32_t *ist)
@@ -599,6 +624,20 @@ HODE_OBS_ABI(f64, double)
 
 HODE_HMC_ABI(f32, float)
 HODE_HMC_ABI(f64, double)
+
+#define HODE_POP_ABI(SFX, R)                                                                                                             \
+    int hode_pop_params_##SFX(void *stream, int A, int B, int K, int ld, const R *coords, uint32_t ode_mask, const double *mu0,       \
+                              const double *sd0, const double *tau0, double tau_log_sd, const R *ode_base, R *ode_p)                  \
+    {                                                                                                                                  \
+        return pop_params<R>(stream, A, B, K, ld, coords, ode_mask, mu0, sd0, tau0, tau_log_sd, ode_base, ode_p);                     \
+    }                                                                                                                                  \
+    int hode_pop_grad_##SFX(void *stream, int A, int B, int K, int ld, const R *coords, const R *gode, uint32_t ode_mask,             \
+                            const double *sd0, const double *tau0, double tau_log_sd, R *glik)                                        \
+    {                                                                                                                                  \
+        return pop_grad<R>(stream, A, B, K, ld, coords, gode, ode_mask, sd0, tau0, tau_log_sd, glik);                                 \
+    }
+HODE_POP_ABI(f32, float)
+HODE_POP_ABI(f64, double)
 
 #define HODE_NUTS_ABI(SFX, R)                                                                                                            \
     int hode_nuts_begin_##SFX(void *stream, int C, int D, int ld, const R *z, const R *p, const R *g, const double *U,                \

@@ -169,6 +169,12 @@ template <typename R> int launch_hmc_leapfrog(hipStream_t s, const HmcLeapfrogAr
 template <typename R> int launch_hmc_accept(hipStream_t s, const HmcAcceptArgs<R> &a);
 template <typename R> int launch_hmc_welford(hipStream_t s, int C, int D, int ld, int flags, const R *z, double *wf, R *minv);
 
+// ---- population model (hode_population.hip): chain coordinates [A][ld] <-> per-(row, patient) constants [A * B][17], see include/hode.h
+template <typename R> int launch_pop_params(hipStream_t s, int A, int B, int K, int ld, const R *coords, uint32_t ode_mask, const double *mu0,
+                                            const double *sd0, const double *tau0, double tau_log_sd, const R *ode_base, R *ode_p);
+template <typename R> int launch_pop_grad(hipStream_t s, int A, int B, int K, int ld, const R *coords, const R *gode, uint32_t ode_mask,
+                                          const double *sd0, const double *tau0, double tau_log_sd, R *glik);
+
 // ---- MCMC (hode_nuts.hip): the per-chain passes of multi-chain No-U-Turn sampling; tree [HODE_NUTS_ROWS][C][ld], see include/hode.h
 template <typename R> struct NutsPreArgs {
     int C, D, ld, n_ode, sample_nn, P;

@@ -31,7 +31,8 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64", "hode_sobol_indices_f32", "hode_sobol_indices_f64",
            "hode_pred_fold_f32", "hode_pred_fold_f64", "hode_pred_score_f32", "hode_pred_score_f64",
            "hode_pred_tails_f32", "hode_pred_tails_f64", "hode_pred_quantiles_f32", "hode_pred_quantiles_f64",
-           "hode_pred_loo_fold_f32", "hode_pred_loo_fold_f64", "hode_pred_loo_finish_f32", "hode_pred_loo_finish_f64"]
+           "hode_pred_loo_fold_f32", "hode_pred_loo_fold_f64", "hode_pred_loo_finish_f32", "hode_pred_loo_finish_f64",
+           "hode_pop_params_f32", "hode_pop_params_f64", "hode_pop_grad_f32", "hode_pop_grad_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -732,6 +733,20 @@ def hmc_accept(C_, D, ld, mode, seed, it, target_accept, z, z0, g, g0, U, U0, ke
 def hmc_welford(C_, D, ld, flags, z, wf, minv):
     _check(getattr(load(), f"hode_hmc_welford_{_sfx(minv.dtype)}")(
         _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(flags), _ptr(z), _ptr(wf), _ptr(minv)), "hode_hmc_welford")
+
+
+def pop_params(A, B, K, ld, coords, ode_mask, mu0, sd0, tau0, tau_log_sd, ode_base, ode_p):
+    """The population map of the first A rows of coords [., ld] into ode_p [A * B, 17] (include/hode.h "Population model")."""
+    _check(getattr(load(), f"hode_pop_params_{_sfx(coords.dtype)}")(
+        _stream(), C.c_int(A), C.c_int(B), C.c_int(K), C.c_int(ld), _ptr(coords), C.c_uint32(ode_mask), _ptr(mu0), _ptr(sd0), _ptr(tau0),
+        C.c_double(tau_log_sd), _ptr(ode_base), _ptr(ode_p)), "hode_pop_params")
+
+
+def pop_grad(A, B, K, ld, coords, gode, ode_mask, sd0, tau0, tau_log_sd, glik):
+    """The transposed population map: gode [A * B, 17] -> the likelihood gradient glik [A, ld] of the first A rows of coords."""
+    _check(getattr(load(), f"hode_pop_grad_{_sfx(coords.dtype)}")(
+        _stream(), C.c_int(A), C.c_int(B), C.c_int(K), C.c_int(ld), _ptr(coords), _ptr(gode), C.c_uint32(ode_mask), _ptr(sd0), _ptr(tau0),
+        C.c_double(tau_log_sd), _ptr(glik)), "hode_pop_grad")
 
 
 NUTS_ROWS, NUTS_MAX_DEPTH = 15, 30

@@ -66,36 +66,17 @@ class _Sampler:
         dev = self.dev = _compute_device()
         nl = model.nn_residual
         self.H, self.L = nl.hidden_dim, nl.hip_layers
-        self.P = hode.n_params(self.H, self.L)
         self.method = _method(solver)
         self.rtol, self.atol, self.seed, self.jitter = float(rtol), float(atol), int(seed) & (2 ** 64 - 1), float(jitter)
-        priors = dict(REFERENCE_PRIORS if ode_priors is None else ode_priors)
-        for k in priors:
-            if k not in ODE_PARAM_NAMES:
-                raise ValueError(f"unknown mechanistic constant {k!r}; known: {list(ODE_PARAM_NAMES)}")
-        self.ode_names = [n for n in ODE_PARAM_NAMES if n in priors]           # ascending ODE index = z order
-        self.ode_mask = sum(1 << ODE_PARAM_NAMES.index(n) for n in self.ode_names)
-        self.n_ode, self.sample_nn = len(self.ode_names), bool(sample_nn)
-        self.nn_names = [(n, tuple(p.shape)) for n, p in nl.named_parameters()]
-        self.D = self.n_ode + (self.P if self.sample_nn else 0)
-        if self.D == 0:
-            raise ValueError("nothing to sample: no ode_priors and sample_nn=False")
-        self.ld = (self.D + 3) // 4 * 4
         C = self.C = int(n_chains)
         f64 = dict(dtype=torch.float64, device=dev)
-        self.mu = torch.tensor([float(priors[n][0]) for n in self.ode_names] or [0.0], **f64)
-        self.sd = torch.tensor([float(priors[n][1]) for n in self.ode_names] or [1.0], **f64)
+        R = dict(dtype=dtype, device=dev)
+        self._layout(ode_priors, sample_nn)
+        self.ld = (self.D + 3) // 4 * 4
         with torch.no_grad():
             nn0, ode0 = model._params_on(dev)
         self.nn_base, self.ode_base = nn0.detach().to(dtype).contiguous(), ode0.detach().to(dtype).contiguous()
-        self.nn_p = self.nn_base.repeat(C).contiguous()
-        self.ode_p = self.ode_base.repeat(C).contiguous()
-        R = dict(dtype=dtype, device=dev)
-        z = torch.zeros(C, self.ld, **R)
-        for i, n in enumerate(self.ode_names):
-            z[:, i] = (float(self.ode_base[ODE_PARAM_NAMES.index(n)]) - float(self.mu[i])) / float(self.sd[i])
-        if self.sample_nn:
-            z[:, self.n_ode:self.D] = self.nn_base
+        z = self._start()
         self.z, self.p, self.g = z, torch.zeros(C, self.ld, **R), torch.zeros(C, self.ld, **R)
         self.z0, self.g0 = torch.zeros_like(z), torch.zeros_like(z)
         self.minv = torch.ones(self.ld, **R)
@@ -127,6 +108,39 @@ class _Sampler:
                                self.rtol, self.atol)          # what _run_sets takes: the batch and the chains' parameter buffers
         self.gnn = self.gode = None
 
+    # ------------------------------------------------------------------ the coordinate layout (inference/population.py replaces it)
+    def _layout(self, ode_priors, sample_nn):
+        """What a chain's D coordinates are: the sampled constants (names, mask, prior mu / sd) and, with sample_nn, the P weights."""
+        from models.ode_core import ODE_PARAM_NAMES
+        self.P = hode.n_params(self.H, self.L)
+        priors = dict(REFERENCE_PRIORS if ode_priors is None else ode_priors)
+        for k in priors:
+            if k not in ODE_PARAM_NAMES:
+                raise ValueError(f"unknown mechanistic constant {k!r}; known: {list(ODE_PARAM_NAMES)}")
+        self.ode_names = [n for n in ODE_PARAM_NAMES if n in priors]           # ascending ODE index = z order
+        self.ode_mask = sum(1 << ODE_PARAM_NAMES.index(n) for n in self.ode_names)
+        self.n_ode, self.sample_nn = len(self.ode_names), bool(sample_nn)
+        self.nn_names = [(n, tuple(p.shape)) for n, p in self.model.nn_residual.named_parameters()]
+        self.D = self.n_ode + (self.P if self.sample_nn else 0)
+        if self.D == 0:
+            raise ValueError("nothing to sample: no ode_priors and sample_nn=False")
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        self.mu = torch.tensor([float(priors[n][0]) for n in self.ode_names] or [0.0], **f64)
+        self.sd = torch.tensor([float(priors[n][1]) for n in self.ode_names] or [1.0], **f64)
+
+    def _start(self):
+        """The chains' parameter buffers nn_p / ode_p and -> z [C, ld] at the model's own parameters."""
+        from models.ode_core import ODE_PARAM_NAMES
+        C = self.C
+        self.nn_p = self.nn_base.repeat(C).contiguous()
+        self.ode_p = self.ode_base.repeat(C).contiguous()
+        z = torch.zeros(C, self.ld, dtype=self.dt, device=self.dev)
+        for i, n in enumerate(self.ode_names):
+            z[:, i] = (float(self.ode_base[ODE_PARAM_NAMES.index(n)]) - float(self.mu[i])) / float(self.sd[i])
+        if self.sample_nn:
+            z[:, self.n_ode:self.D] = self.nn_base
+        return z
+
     # ------------------------------------------------------------------ the pieces of an iteration
     def evaluate(self, n_sets=None):
         """Likelihood sum of squares, its gradient and the solve statuses at the parameters in nn_p / ode_p: of all chains, or
@@ -135,9 +149,15 @@ class _Sampler:
         budget (models.hybrid_ode_nn._run_sets; this class supplies the cotangent of a piece)."""
         if not self.has_data:
             return
+        _, self.gnn, self.gode = self._run_pieces(self.C if n_sets is None else int(n_sets), (False, self.sample_nn, self.n_ode > 0))
+
+    def _run_pieces(self, C, want, max_traj=None, **run_kw):
+        """loss_sum, the statuses and the gradients `want` of the first C chains over the pieces of the plan; max_traj and run_kw
+        go to _plan_sets and _run_sets (own_sets: inference/population.py)."""
         import models.hybrid_ode_nn as HN
-        C, N = self.C if n_sets is None else int(n_sets), self.N
-        plan = HN._plan_sets(self.dev, C, N, self.T, self.method, self.x0.element_size(), self.L, self.H, self.model.tape_steps)
+        N = self.N
+        plan = HN._plan_sets(self.dev, C, N, self.T, self.method, self.x0.element_size(), self.L, self.H, self.model.tape_steps,
+                             max_traj=max_traj)
         lo, hi = plan[1][0][2:]
         self.loss_sum.zero_()
         stat = []
@@ -147,11 +167,13 @@ class _Sampler:
             flags = 0
             if self.om.marginal and hi - lo < N:
                 # a set cut into pieces: its cotangent needs the sums of the WHOLE set, so the pieces run once without a tape first
-                HN._run_sets(plan, partial(self._obs_piece, [], hode.capi.OBS_SUMS_ONLY), (False, False, False), *self.solve_args)
+                HN._run_sets(plan, partial(self._obs_piece, [], hode.capi.OBS_SUMS_ONLY), (False, False, False), *self.solve_args,
+                             **run_kw)
                 flags = hode.capi.OBS_FROM_SSE
             cotangent = partial(self._obs_piece, stat, flags)
-        _, self.gnn, self.gode = HN._run_sets(plan, cotangent, (False, self.sample_nn, self.n_ode > 0), *self.solve_args)
+        out = HN._run_sets(plan, cotangent, want, *self.solve_args, **run_kw)
         self.status = (stat[0] if len(stat) == 1 else torch.cat(stat)).view(C, N)
+        return out
 
     def _mse_piece(self, stat, sol, s0, s1, lo, hi):
         stat.append(sol.status)

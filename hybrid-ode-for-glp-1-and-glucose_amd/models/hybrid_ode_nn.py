@@ -239,6 +239,12 @@ class _Taped:
         for k, v in (gi or {}).items():
             if v is not None:
                 gin[k][idx] = v
+        if set_id is None:                       # own sets: trajectory idx[i] is parameter set idx[i] (each at most once)
+            if gn is not None:
+                gnn.view(-1, gn.numel() // idx.numel())[idx] += gn.view(idx.numel(), -1)
+            if go is not None:
+                gode.view(-1, 17)[idx] += go.view(-1, 17)
+            return
         _add_sets(gnn, gode, set_id, set_id + 1, gn, go)
 
 
@@ -251,11 +257,13 @@ def _add_sets(gnn, gode, s0, s1, gn, go):
         gode[17 * s0:17 * s1] += go
 
 
-def _solve_taped(x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol, n_sets, steps, tape=None):
+def _solve_taped(x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol, n_sets, steps, tape=None, own_sets=False):
     """Forward solve with a tape of `steps` accepted steps per trajectory; status-1 trajectories (budget exhausted) are
     solved again, set by set, with the inference budget and their rows replace the truncated ones.  One host
     synchronisation (the failure count); no second launch in the common case.  The retries' tapes count against the tape
-    budget: what does not fit is integrated without a tape now and re-integrated piecewise in the backward (_Taped)."""
+    budget: what does not fit is integrated without a tape now and re-integrated piecewise in the backward (_Taped).
+    own_sets (n_sets == trajectories, _run_sets): the status-1 trajectories are solved again in ONE launch, each with its own
+    parameter rows (set id None in `extras`), instead of one launch per set."""
     sol = hode.solve_fwd(x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method=method, rtol=rtol, atol=atol, n_sets=n_sets,
                          want_tape=tape is None, tape=tape, max_steps=steps)
     extras = []
@@ -269,17 +277,22 @@ def _solve_taped(x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, at
             cut = lambda v, i: None if v is None else v[i].contiguous()          # noqa: E731
             per_traj = hode.capi.tape_nbytes(1, big, x0.element_size(), L, H)
             left = _tape_budget(x0.device)
-            for set_id in torch.unique(bad // per_set).tolist():
-                idx = bad[(bad // per_set) == set_id]
+            own = own_sets and per_set == 1
+            for set_id in ([None] if own else torch.unique(bad // per_set).tolist()):
+                idx = bad if own else bad[(bad // per_set) == set_id]
                 xs, ts = x0[idx].contiguous(), (t[idx].contiguous() if t.dim() == 2 else t)
                 ms, vs, gs = cut(meal, idx), cut(tvns, idx), cut(gd, idx)
-                o1, n1 = ode_vec[17 * set_id:17 * (set_id + 1)], nn_flat[P * set_id:P * (set_id + 1)]
+                if own:                          # the rows of the retried trajectories' own sets
+                    o1, n1 = ode_vec.view(-1, 17)[idx].contiguous(), nn_flat.view(-1, P)[idx].contiguous()
+                else:
+                    o1, n1 = ode_vec[17 * set_id:17 * (set_id + 1)], nn_flat[P * set_id:P * (set_id + 1)]
 
-                def solve(sl=None, tp=None, want=True, xs=xs, ts=ts, ms=ms, vs=vs, gs=gs, o1=o1, n1=n1):
+                def solve(sl=None, tp=None, want=True, xs=xs, ts=ts, ms=ms, vs=vs, gs=gs, o1=o1, n1=n1, own=own):
                     c2 = lambda v: None if v is None else (v if sl is None else v[sl].contiguous())   # noqa: E731
-                    return hode.solve_fwd(c2(xs), c2(ts) if ts.dim() == 2 else ts, c2(ms), c2(vs), c2(gs), o1, n1, H, L, method=method,
-                                          rtol=rtol, atol=atol, n_sets=1, want_tape=want and tp is None, tape=tp if want else None,
-                                          max_steps=big)
+                    o, n = (c2(o1).reshape(-1), c2(n1).reshape(-1)) if own else (o1, n1)
+                    return hode.solve_fwd(c2(xs), c2(ts) if ts.dim() == 2 else ts, c2(ms), c2(vs), c2(gs), o, n, H, L, method=method,
+                                          rtol=rtol, atol=atol, n_sets=c2(xs).shape[0] if own else 1, want_tape=want and tp is None,
+                                          tape=tp if want else None, max_steps=big)
                 fits = idx.numel() * per_traj <= left
                 s2 = solve(want=fits)
                 if fits:
@@ -381,13 +394,19 @@ def _pieces(n_sets, G, cap):
     return [(s, s + 1, a, min(a + cap, G)) for s in range(n_sets) for a in range(0, G, cap)]
 
 
-def _plan_sets(dev, n_sets, G, T, method, elem, L, H, tape_steps=None, grads=True):
+OWN_SETS_MAX = 1024              # sets of one launch when every trajectory is its own set: above, the adjoint's reduction uses atomics
+
+
+def _plan_sets(dev, n_sets, G, T, method, elem, L, H, tape_steps=None, grads=True, max_traj=None):
     """(accepted-step budget of the taped solves, pieces of _pieces) for n_sets parameter sets x G shared patients on a grid of
-    T points under the tape budget.  Without gradients nothing is taped: one piece."""
+    T points under the tape budget.  Without gradients nothing is taped: one piece.  max_traj additionally caps the
+    trajectories of a piece (_run_sets with own_sets: OWN_SETS_MAX)."""
+    most = n_sets * G if max_traj is None else min(n_sets * G, int(max_traj))
     if not grads:
-        return _tape_steps(T, method, tape_steps), _pieces(n_sets, G, n_sets * G)
+        return _tape_steps(T, method, tape_steps), _pieces(n_sets, G, most)
     steps = _taped_steps(n_sets * G, T, method, elem, L, H, tape_steps)
-    return steps, _pieces(n_sets, G, _tape_cap(dev, steps, elem, L, H, n_sets * G))
+    cap = _tape_cap(dev, steps, elem, L, H, n_sets * G)
+    return steps, _pieces(n_sets, G, cap if max_traj is None else min(cap, most))
 
 
 def _rep(v, lo, hi, m):
@@ -398,27 +417,45 @@ def _rep(v, lo, hi, m):
     return v.repeat(m, *([1] * (v.dim() - 1))) if m > 1 else v
 
 
-def _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol):
+def _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol, own_sets=False):
     """A likelihood of parameter sets (ode_vec, nn_flat) x the patients (x0, t, meal, tvns, gd: shared by the sets) and its
     gradient in one pass over the pieces of `plan` (_plan_sets): forward solve with tape (one tape buffer, handed from piece to
     piece) -> gy = cotangent(sol, s0, s1, lo, hi), the caller's likelihood of the sets s0..s1-1 x the patients lo..hi-1 at sol.y
     (it may keep sol's statuses or y) -> adjoint.  -> (gx0 summed over the sets, gnn, gode) where want = (gx0, gnn, gode) asks;
-    with nothing wanted the solves are plain forward solves and `cotangent` only accumulates."""
+    with nothing wanted the solves are plain forward solves and `cotangent` only accumulates.
+
+    own_sets (inference/population.py): every trajectory of a piece is its own parameter set of the kernels.  ode_vec then holds
+    one row per (set, patient), the rows of the sets s0..s1-1 x the patients lo..hi-1 being the contiguous rows s G + lo ..; gode
+    comes back with the same rows.  nn_flat is ONE network: it is replicated per piece into one buffer, sized for the largest
+    piece and handed from piece to piece like the tape (trajectories of the piece x P reals), and gnn cannot be asked for.  The
+    plan's pieces hold at most OWN_SETS_MAX trajectories (_plan_sets(..., max_traj=OWN_SETS_MAX))."""
     steps, pieces = plan
     grads, one, n_sets = any(want), len(pieces) == 1, pieces[-1][1]
     P = hode.n_params(H, L)
+    G = x0.shape[0]
+    if own_sets and want[1]:
+        raise ValueError("own_sets shares one network among the trajectories: there is no per-set network gradient")
     gx0 = torch.zeros_like(x0) if want[0] else None
     gnn = nn_flat.new_zeros(n_sets * P) if want[1] and not one else None
-    gode = ode_vec.new_zeros(n_sets * 17) if want[2] and not one else None
-    tape = None
+    gode = ode_vec.new_zeros(n_sets * (G if own_sets else 1) * 17) if want[2] and not one else None
+    tape = nn_rep = None
     for s0, s1, lo, hi in pieces:
         m = s1 - s0
+        r0, r1, k = s0, s1, m                          # the kernels' parameter sets of this piece: rows r0..r1-1 of ode_vec
+        nn_piece = nn_flat if own_sets else nn_flat[P * s0:P * s1]
+        if own_sets:
+            k = m * (hi - lo)
+            r0 = s0 * G + lo
+            r1 = r0 + k
+            if nn_rep is None:
+                nn_rep = nn_flat.repeat(k)             # largest piece first: later ones fit
+            nn_piece = nn_rep[:P * k]
         args = (_rep(x0, lo, hi, m), t if t.dim() == 1 else _rep(t, lo, hi, m), _rep(meal, lo, hi, m), _rep(tvns, lo, hi, m),
-                _rep(gd, lo, hi, m), ode_vec[17 * s0:17 * s1], nn_flat[P * s0:P * s1], H, L)
+                _rep(gd, lo, hi, m), ode_vec[17 * r0:17 * r1], nn_piece, H, L)
         if not grads:
-            cotangent(hode.solve_fwd(*args, method=method, rtol=rtol, atol=atol, n_sets=m), s0, s1, lo, hi)
+            cotangent(hode.solve_fwd(*args, method=method, rtol=rtol, atol=atol, n_sets=k), s0, s1, lo, hi)
             continue
-        sol = _solve_taped(*args, method, rtol, atol, m, steps, tape=tape)
+        sol = _solve_taped(*args, method, rtol, atol, k, steps, tape=tape, own_sets=own_sets)
         tape = sol.tape
         g0, gn, go = sol.backward(cotangent(sol, s0, s1, lo, hi), want_gnn=want[1], want_gode=want[2])
         if gx0 is not None:
@@ -426,7 +463,7 @@ def _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H,
         if one:
             gnn, gode = gn, go                     # (the whole batch in one launch: the adjoint's buffers ARE the result)
         else:
-            _add_sets(gnn, gode, s0, s1, gn, go)
+            _add_sets(gnn, gode, r0, r1, gn, go)
     return gx0, gnn, gode
 
 

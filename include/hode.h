@@ -500,6 +500,31 @@ int hode_nuts_finish_f64(void *stream, int C, int D, int ld, int adapt, double t
                          const double *tree, const double *dst, const int32_t *ist, double *log_eps, double *da, int n_ode,
                          const double *mu, const double *sd, double *draws, double *stats, int n_slots, int slot);
 
+/* ---- Population model (inference/population.py, run_population): a reparameterisation layer between the samplers' chain
+ *      coordinates and the solve's per-set constants.  K sampled constants (the set bits of ode_mask, ascending), B patients.
+ *      A row of coords [A][ld] (ld >= D = K (B + 2), DEVICE) holds, each with an N(0, 1) prior,
+ *          [ m_0..m_{K-1} | s_0..s_{K-1} | z_{0,0}..z_{0,K-1} | ... | z_{B-1,0}..z_{B-1,K-1} ]
+ *      and means
+ *          mu_pop_k = mu0_k + sd0_k m_k,   tau_k = tau0_k exp(tau_log_sd s_k),   theta_{b,k} = mu_pop_k + tau_k z_{b,k}.
+ *      mu0, sd0, tau0: fp64 [K], DEVICE.  Everything is computed in double and rounded once.
+ *   - pop_params: ode_p[A * B][17], set a * B + b = patient b of row a; ALL 17 entries are written, the unsampled ones from
+ *     ode_base[17].
+ *   - pop_grad: the transpose.  With G_{b,k} = gode[a * B + b][ODE index of k] (the adjoint's per-set gradient):
+ *          glik[a][k] = sd0_k sum_b G_{b,k},  glik[a][K + k] = tau_log_sd tau_k sum_b G_{b,k} z_{b,k},
+ *          glik[a][2 K + b K + k] = tau_k G_{b,k};  entries D..ld-1 are written as 0.
+ *     One workgroup per row, lane t sums the patients t, t + 256, ... in ascending order in fp64, then the fixed order of the
+ *     chain reductions above; no floating-point atomics: the same call gives the same bits, and a row's result depends neither
+ *     on A nor on the row's index.
+ *   A == 0: HODE_OK, nothing launched.  HODE_EINVAL: K < 1, K > 17, popcount(ode_mask) != K, B < 1, ld < K (B + 2), a NULL. */
+int hode_pop_params_f32(void *stream, int A, int B, int K, int ld, const float *coords, uint32_t ode_mask, const double *mu0,
+                        const double *sd0, const double *tau0, double tau_log_sd, const float *ode_base, float *ode_p);
+int hode_pop_params_f64(void *stream, int A, int B, int K, int ld, const double *coords, uint32_t ode_mask, const double *mu0,
+                        const double *sd0, const double *tau0, double tau_log_sd, const double *ode_base, double *ode_p);
+int hode_pop_grad_f32(void *stream, int A, int B, int K, int ld, const float *coords, const float *gode, uint32_t ode_mask,
+                      const double *sd0, const double *tau0, double tau_log_sd, float *glik);
+int hode_pop_grad_f64(void *stream, int A, int B, int K, int ld, const double *coords, const double *gode, uint32_t ode_mask,
+                      const double *sd0, const double *tau0, double tau_log_sd, double *glik);
+
 /* =====================================================================================================
  * Sobol indices (inference/sobol.py, sobol_indices / sobol_study): the analysis half of the sensitivity study of the
  * reference's plots/plot_all.py:139-224, i.e. what SALib.analyze.sobol.analyze computes from the model outputs of a
