@@ -265,6 +265,36 @@ template <typename R> int pop_grad(void *stream, int A, int B, int K, int ld, co
     return launch_pop_grad<R>((hipStream_t)stream, A, B, K, ld, coords, gode, ode_mask, sd0, tau0, tau_log_sd, glik);
 }
 
+// ---- initial-state model (hode_x0.hip)
+inline bool x0_ok(int A, int B, int n_lat, int ld, int off, uint32_t lat_mask, int link, int K, uint32_t ode_mask, bool with_ode)
+{
+    if (A < 1 || B < 1 || n_lat < 1 || n_lat > 6 || (lat_mask >> 6) || __builtin_popcount(lat_mask) != n_lat) return false;
+    if (K < 0 || K > 17 || (ode_mask >> 17) || __builtin_popcount(ode_mask) != K || (link != 0 && link != 1)) return false;
+    if (off < 0 || (with_ode && off < K) || ld < off + (int64_t)B * n_lat) return false;
+    return (int64_t)A * ld <= ((int64_t)1 << 40) && (int64_t)A * B <= ((int64_t)1 << 36) && B <= (1 << 21);   // (tiles in grid.y)
+}
+
+template <typename R> int x0_params(void *stream, int A, int B, int n_lat, int ld, int off, const R *coords, uint32_t lat_mask, int link,
+                                    const double *m, const double *s, const R *x0_base, R *x0_out, int K, uint32_t ode_mask,
+                                    const double *mu, const double *sd, const R *ode_base, R *ode_p)
+{
+    if (!x0_ok(A, B, n_lat, ld, off, lat_mask, link, K, ode_mask, ode_p != nullptr)) return HODE_EINVAL;
+    if (!coords || !m || !s || !x0_base || !x0_out) return HODE_EINVAL;
+    if (ode_p && (!ode_base || (K > 0 && (!mu || !sd)))) return HODE_EINVAL;
+    return launch_x0_params<R>((hipStream_t)stream, A, B, n_lat, ld, off, coords, lat_mask, link, m, s, x0_base, x0_out, ode_mask, mu, sd,
+                               ode_base, ode_p);
+}
+
+template <typename R> int x0_grad(void *stream, int A, int B, int n_lat, int ld, int off, const R *coords, uint32_t lat_mask, int link,
+                                  const double *m, const double *s, const R *gx0, int K, uint32_t ode_mask, const double *sd, const R *gode,
+                                  R *glik)
+{
+    if (!x0_ok(A, B, n_lat, ld, off, lat_mask, link, K, ode_mask, gode != nullptr)) return HODE_EINVAL;
+    if (!coords || !m || !s || !gx0 || !glik) return HODE_EINVAL;
+    if (gode && K > 0 && !sd) return HODE_EINVAL;
+    return launch_x0_grad<R>((hipStream_t)stream, A, B, n_lat, ld, off, coords, lat_mask, link, m, s, gx0, K, ode_mask, sd, gode, glik);
+}
+
 // ---- No-U-Turn sampling (hode_nuts.hip)
 template <typename R> int nuts_begin(void *stream, int C, int D, int ld, const R *z, const R *p, const R *g, const double *U, const double *U0,
                                      const double *ke0, R *tree, double *dst, int32_t *ist)
@@ -638,6 +668,23 @@ HODE_HMC_ABI(f64, double)
     }
 HODE_POP_ABI(f32, float)
 HODE_POP_ABI(f64, double)
+
+#define HODE_X0_ABI(SFX, R)                                                                                                              \
+    int hode_x0_params_##SFX(void *stream, int A, int B, int n_lat, int ld, int off, const R *coords, uint32_t lat_mask, int link,     \
+                             const double *m, const double *s, const R *x0_base, R *x0_out, int K, uint32_t ode_mask,                  \
+                             const double *mu, const double *sd, const R *ode_base, R *ode_p)                                         \
+    {                                                                                                                                  \
+        return x0_params<R>(stream, A, B, n_lat, ld, off, coords, lat_mask, link, m, s, x0_base, x0_out, K, ode_mask, mu, sd,         \
+                            ode_base, ode_p);                                                                                          \
+    }                                                                                                                                  \
+    int hode_x0_grad_##SFX(void *stream, int A, int B, int n_lat, int ld, int off, const R *coords, uint32_t lat_mask, int link,       \
+                           const double *m, const double *s, const R *gx0, int K, uint32_t ode_mask, const double *sd, const R *gode,  \
+                           R *glik)                                                                                                    \
+    {                                                                                                                                  \
+        return x0_grad<R>(stream, A, B, n_lat, ld, off, coords, lat_mask, link, m, s, gx0, K, ode_mask, sd, gode, glik);              \
+    }
+HODE_X0_ABI(f32, float)
+HODE_X0_ABI(f64, double)
 
 #define HODE_NUTS_ABI(SFX, R)                                                                                                            \
     int hode_nuts_begin_##SFX(void *stream, int C, int D, int ld, const R *z, const R *p, const R *g, const double *U,                \

@@ -175,6 +175,14 @@ template <typename R> int launch_pop_params(hipStream_t s, int A, int B, int K, 
 template <typename R> int launch_pop_grad(hipStream_t s, int A, int B, int K, int ld, const R *coords, const R *gode, uint32_t ode_mask,
                                           const double *sd0, const double *tau0, double tau_log_sd, R *glik);
 
+// ---- initial-state model (hode_x0.hip): chain coordinates [A][ld] <-> per-(row, patient) initial states [A * B][6], see include/hode.h
+template <typename R> int launch_x0_params(hipStream_t s, int A, int B, int n_lat, int ld, int off, const R *coords, uint32_t lat_mask,
+                                           int link, const double *m, const double *sd_x, const R *x0_base, R *x0_out, uint32_t ode_mask,
+                                           const double *mu, const double *sd, const R *ode_base, R *ode_p);
+template <typename R> int launch_x0_grad(hipStream_t s, int A, int B, int n_lat, int ld, int off, const R *coords, uint32_t lat_mask,
+                                         int link, const double *m, const double *sd_x, const R *gx0, int K, uint32_t ode_mask,
+                                         const double *sd, const R *gode, R *glik);
+
 // ---- MCMC (hode_nuts.hip): the per-chain passes of multi-chain No-U-Turn sampling; tree [HODE_NUTS_ROWS][C][ld], see include/hode.h
 template <typename R> struct NutsPreArgs {
     int C, D, ld, n_ode, sample_nn, P;

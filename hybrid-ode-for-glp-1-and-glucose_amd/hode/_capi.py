@@ -32,7 +32,8 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_pred_fold_f32", "hode_pred_fold_f64", "hode_pred_score_f32", "hode_pred_score_f64",
            "hode_pred_tails_f32", "hode_pred_tails_f64", "hode_pred_quantiles_f32", "hode_pred_quantiles_f64",
            "hode_pred_loo_fold_f32", "hode_pred_loo_fold_f64", "hode_pred_loo_finish_f32", "hode_pred_loo_finish_f64",
-           "hode_pop_params_f32", "hode_pop_params_f64", "hode_pop_grad_f32", "hode_pop_grad_f64"]
+           "hode_pop_params_f32", "hode_pop_params_f64", "hode_pop_grad_f32", "hode_pop_grad_f64",
+           "hode_x0_params_f32", "hode_x0_params_f64", "hode_x0_grad_f32", "hode_x0_grad_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -747,6 +748,27 @@ def pop_grad(A, B, K, ld, coords, gode, ode_mask, sd0, tau0, tau_log_sd, glik):
     _check(getattr(load(), f"hode_pop_grad_{_sfx(coords.dtype)}")(
         _stream(), C.c_int(A), C.c_int(B), C.c_int(K), C.c_int(ld), _ptr(coords), _ptr(gode), C.c_uint32(ode_mask), _ptr(sd0), _ptr(tau0),
         C.c_double(tau_log_sd), _ptr(glik)), "hode_pop_grad")
+
+
+X0_LINK_IDENTITY, X0_LINK_LOG = 0, 1
+
+
+def x0_params(A, B, n_lat, ld, off, coords, lat_mask, link, m, s, x0_base, x0_out, K=0, ode_mask=0, mu=None, sd=None, ode_base=None,
+              ode_p=None):
+    """The initial-state map of the first A rows of coords [., ld] into x0_out [A * B, 6] and, with ode_p, the rows' global
+    constants into ode_p [A, 17] (include/hode.h "Initial-state model")."""
+    _check(getattr(load(), f"hode_x0_params_{_sfx(coords.dtype)}")(
+        _stream(), C.c_int(A), C.c_int(B), C.c_int(n_lat), C.c_int(ld), C.c_int(off), _ptr(coords), C.c_uint32(lat_mask), C.c_int(link),
+        _ptr(m), _ptr(s), _ptr(x0_base), _ptr(x0_out), C.c_int(K), C.c_uint32(ode_mask), _ptr(mu), _ptr(sd), _ptr(ode_base),
+        _ptr(ode_p)), "hode_x0_params")
+
+
+def x0_grad(A, B, n_lat, ld, off, coords, lat_mask, link, m, s, gx0, glik, K=0, ode_mask=0, sd=None, gode=None):
+    """The transposed initial-state map: gx0 [A * B, 6] (and gode [A, 17]) -> the entries of the likelihood gradient glik [A, ld]
+    that the layer owns; nothing else of glik is touched."""
+    _check(getattr(load(), f"hode_x0_grad_{_sfx(coords.dtype)}")(
+        _stream(), C.c_int(A), C.c_int(B), C.c_int(n_lat), C.c_int(ld), C.c_int(off), _ptr(coords), C.c_uint32(lat_mask), C.c_int(link),
+        _ptr(m), _ptr(s), _ptr(gx0), C.c_int(K), C.c_uint32(ode_mask), _ptr(sd), _ptr(gode), _ptr(glik)), "hode_x0_grad")
 
 
 NUTS_ROWS, NUTS_MAX_DEPTH = 15, 30

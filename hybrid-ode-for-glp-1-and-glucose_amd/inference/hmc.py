@@ -477,7 +477,8 @@ def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1
             n_leapfrog: int = 16, target_accept: float = 0.8, noise_sigma: float = 1.0,
             ode_priors: Optional[Dict[str, Tuple[float, float]]] = None, sample_nn: bool = True, thin: int = 1, seed: int = 0,
             solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8, device=None, dtype=torch.float32,
-            jitter: float = 0.1, progress=None, noise: str = "fixed", noise_prior=None) -> HMCResult:
+            jitter: float = 0.1, progress=None, noise: str = "fixed", noise_prior=None, initial_state=None,
+            n_patients: Optional[int] = None) -> HMCResult:
     """Sample the posterior of `model` given the batch `data` (None: the prior alone) with n_chains chains.
 
     Observations that are NaN, or false in data["observation_mask"] (bool [B, T, 6]), are missing; a state may be observed
@@ -489,7 +490,17 @@ def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1
     (Stan's windows); then num_samples iterations, every `thin`-th kept.  ode_priors: name -> (mean, std) of the sampled
     mechanistic constants (default: the reference's seven); sample_nn: sample every MLP weight (prior N(0, 1)).  `device` is
     accepted for run_nuts compatibility: the work runs on the HIP device.  `progress(it, stats)`, if given, is called once per
-    iteration (one host synchronisation)."""
+    iteration (one host synchronisation).
+
+    initial_state: an `inference.initial_state.InitialStatePrior` makes the chosen components of every patient's initial state
+    latent (sample_nn must be False; ode_priors={} samples the states alone; data=None needs n_patients) -> LatentStateResult."""
+    if initial_state is not None:
+        from inference.initial_state import _run_latent
+        return _run_latent("hmc", model, data, initial_state, num_samples=num_samples, num_warmup=num_warmup, n_chains=n_chains,
+                           n_leapfrog=n_leapfrog, target_accept=target_accept, noise_sigma=noise_sigma, ode_priors=ode_priors,
+                           sample_nn=sample_nn, thin=thin, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter,
+                           progress=progress, noise=noise, noise_prior=noise_prior, n_patients=n_patients)
+
     def transition(s, it, warm, draws, stats, n_slots, slot):
         s.refresh(it)
         s.trajectory(n_leapfrog)

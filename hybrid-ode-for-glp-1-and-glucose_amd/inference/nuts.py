@@ -69,7 +69,7 @@ def run_nuts(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 
              target_accept: float = 0.8, max_tree_depth: int = 10, device=None, *, n_chains: int = 64, noise_sigma: float = 1.0,
              ode_priors: Optional[Dict[str, Tuple[float, float]]] = None, sample_nn: bool = True, thin: int = 1, seed: int = 0,
              solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8, dtype=torch.float32, jitter: float = 0.1,
-             progress=None, noise: str = "fixed", noise_prior=None) -> HMCResult:
+             progress=None, noise: str = "fixed", noise_prior=None, initial_state=None, n_patients: Optional[int] = None) -> HMCResult:
     """Sample the posterior of `model` given the batch `data` (None: the prior alone) with n_chains chains of NUTS.
 
     The target, priors, observation model (missing observations, noise_sigma per state, noise="marginal" / noise_prior) and
@@ -79,7 +79,15 @@ def run_nuts(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 
     reference's signature: the work runs on the HIP device.  `progress(it, stats)`, if given, is called once per iteration.
 
     The result's stats add tree_depth and n_leapfrog [chains, draws] (int) to run_hmc's, accept_prob is the tree's accept
-    statistic, and trajectories_solved [iterations] counts the solves of every sampling and warm-up iteration."""
+    statistic, and trajectories_solved [iterations] counts the solves of every sampling and warm-up iteration.
+
+    initial_state: an `inference.initial_state.InitialStatePrior`, as in run_hmc -> LatentStateResult."""
+    if initial_state is not None:
+        from inference.initial_state import _run_latent
+        return _run_latent("nuts", model, data, initial_state, num_samples=num_samples, num_warmup=num_warmup, n_chains=n_chains,
+                           max_tree_depth=max_tree_depth, target_accept=target_accept, noise_sigma=noise_sigma, ode_priors=ode_priors,
+                           sample_nn=sample_nn, thin=thin, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter,
+                           progress=progress, noise=noise, noise_prior=noise_prior, n_patients=n_patients)
     solved = []
 
     def transition(s, it, warm, draws, stats, n_slots, slot):

@@ -168,11 +168,14 @@ class PopulationResult:
     / run_nuts's; `predict`, `predict_new`, `predictive_summary`: the posterior predictive of the run's patients or of new ones."""
 
     def __init__(self, draws, names, n_patients, mu0, sd0, tau0, tau_log_sd=0.5, stats=None, model=None, ode_base=None, nn_base=None,
-                 observation=None, data=None):
+                 observation=None, data=None, latent=None):
         self.draws = torch.as_tensor(draws)
         self.names, self.B, self.K = list(names), int(n_patients), len(names)
-        if self.draws.dim() != 3 or self.draws.shape[2] != layout(self.K, self.B)["D"]:
-            raise ValueError(f"draws must be [chains, draws, K (B + 2)] = [., ., {layout(self.K, self.B)['D']}]")
+        self.latent = latent                     # the bound InitialStatePrior of a run with initial_state (inference/initial_state.py)
+        n_w = 0 if latent is None else latent.B * latent.n_lat
+        if self.draws.dim() != 3 or self.draws.shape[2] != layout(self.K, self.B)["D"] + n_w:
+            raise ValueError(f"draws must be [chains, draws, K (B + 2)] = [., ., {layout(self.K, self.B)['D']}]" +
+                             (f" + B n_lat = {n_w}" if n_w else ""))
         f64 = lambda v: torch.as_tensor(v, dtype=torch.float64).reshape(self.K)          # noqa: E731
         self.mu0, self.sd0, self.tau0, self.omega = f64(mu0), f64(sd0), f64(tau0), float(tau_log_sd)
         self.stats = stats if stats is not None else {}
@@ -205,6 +208,19 @@ class PopulationResult:
         """theta_{b,k} of every draw, [C, n, B, K] in natural units (fp64, on the draws' device)."""
         return self.population()["mu"].unsqueeze(2) + self._offsets()
 
+    def initial_states(self) -> torch.Tensor:
+        """x0 of every draw of a run with initial_state, [C, n, B, 6] (fp64, on the draws' device): the latent entries from the
+        draws' w columns (from K (B + 2)), the others from the batch."""
+        if self.latent is None:
+            raise ValueError("the run had no latent initial state (run_population(initial_state=...))")
+        return self.latent.fill(self.latent.natural(self.draws[..., layout(self.K, self.B)["D"]:]))
+
+    def _x0_rows(self, thin, x0):
+        """What _solve_rows takes as x0: the batch's rows, or [S, B, 6] of the kept draws' own initial states."""
+        if self.latent is None or x0 is None:
+            return x0
+        return self.initial_states()[:, ::thin].reshape(-1, self.B, 6).to(torch.float32)
+
     def _natural(self) -> HMCResult:
         """The natural quantities as an HMCResult whose "weights" are pop.mu.<name>, pop.tau.<name> (scalars) and
         patient.<name> ([B]): its samples / rhat / ess / summary are this result's."""
@@ -214,7 +230,12 @@ class PopulationResult:
             th = self.patients().transpose(2, 3).reshape(C, n, self.K * self.B)          # [k][b]
             keys = ([(f"pop.mu.{k}", ()) for k in self.names] + [(f"pop.tau.{k}", ()) for k in self.names] +
                     [(f"patient.{k}", (self.B,)) for k in self.names])
-            self._nat = HMCResult(torch.cat([pop["mu"], pop["tau"], th], 2), [], keys, self.stats)
+            cols = [pop["mu"], pop["tau"], th]
+            if self.latent is not None:          # x0.<state> [B] of the latent entries
+                lat = self.latent
+                cols.append(self.initial_states()[..., lat.states].transpose(2, 3).reshape(C, n, lat.n_lat * self.B))
+                keys += [(f"x0.{st}", (self.B,)) for st in lat.state_names]
+            self._nat = HMCResult(torch.cat(cols, 2), [], keys, self.stats)
         return self._nat
 
     @property
@@ -273,9 +294,12 @@ class PopulationResult:
         -> (y [S, B, T, 6], status [S, B]) on the compute device."""
         from inference.predictive import _rep_inputs
         m = self.model
+        own = x0.dim() == 3                      # [S, B, 6]: every draw's own initial states
         x0 = x0.unsqueeze(0) if x0.dim() == 1 else x0
-        B = x0.shape[0]
-        xs, ts, us = _rep_inputs(S, x0, t_span, external_inputs)
+        B = x0.shape[-2]
+        xs, ts, us = _rep_inputs(S, x0[0] if own else x0, t_span, external_inputs)
+        if own:
+            xs = x0.reshape(S * B, 6)
         with torch.no_grad():
             y = m._solve(xs, ts, us, solver, rtol, atol, n_sets=S * B, nn_flat=self.nn_base.to(ode.device, torch.float32),
                          ode_vec=ode.reshape(-1).contiguous(), nn_shared=True)
@@ -304,8 +328,8 @@ class PopulationResult:
             raise ValueError("predict needs the run's batch: the run had none (predict_new takes one)")
         th = self._kept(thin)
         d = self.data
-        y, _ = self._solve_rows(self._ode_rows(th), th.shape[0], d["initial_state"], d["time_points"], d.get("external_inputs"), solver,
-                                rtol, atol)
+        y, _ = self._solve_rows(self._ode_rows(th), th.shape[0], self._x0_rows(thin, d["initial_state"]), d["time_points"],
+                                d.get("external_inputs"), solver, rtol, atol)
         return y.to(self.model.device)
 
     def predict_new(self, initial_state, t_span, external_inputs=None, thin=1, seed=0, solver="dopri5", rtol=1e-6, atol=1e-8):
@@ -326,6 +350,7 @@ class PopulationResult:
         (`predict_new`'s constants); otherwise they are the run's patients, in order."""
         from inference import predictive as PR
         self._need_model()
+        own_x0 = self.latent is not None and not new_patients and (batch is None or batch is self.data)
         batch = self.data if batch is None else batch
         if batch is None:
             raise ValueError("predictive_summary needs a batch: the run had none")
@@ -337,12 +362,14 @@ class PopulationResult:
         th = self._new(thin, Bn, seed) if new_patients else self._kept(thin)
         S = th.shape[0]
         ode = self._ode_rows(th).view(S, Bn, 17)
+        xs = self._x0_rows(thin, x0) if own_x0 else None          # [S, B, 6]: every draw's own initial states
         # the run's fixed observation noise enters the PIT and std; an inferred one (noise="marginal") is not drawn here
         sig = None if self.observation is None or self.observation.marginal else self.observation.sigma
         acc = PR.PredictiveAccumulator(Bn, T, batch.get("observations"), batch.get("observation_mask"), torch.float32, quantiles=quantiles,
                                        expected_draws=None if quantiles is None else max(S, 1))
         for lo, hi in PR.cut_draws(S, Bn * T * 6 * 4, PR._DEFAULT_MAX_BYTES if max_bytes is None else max_bytes):
-            y, status = self._solve_rows(ode[lo:hi], hi - lo, x0, batch["time_points"], batch.get("external_inputs"), solver, rtol, atol)
+            y, status = self._solve_rows(ode[lo:hi], hi - lo, xs[lo:hi] if own_x0 else x0, batch["time_points"],
+                                         batch.get("external_inputs"), solver, rtol, atol)
             acc.fold(y, sig, status)
             del y
         return acc.finish(n_bins)
@@ -354,7 +381,7 @@ def run_population(model, data: Optional[Dict[str, torch.Tensor]], num_samples: 
                    noise_sigma: float = 1.0, ode_priors: Optional[Dict[str, Tuple[float, float]]] = None, tau_scale=None,
                    tau_log_sd: float = 0.5, init=None, thin: int = 1, seed: int = 0, solver: str = "dopri5", rtol: float = 1e-6,
                    atol: float = 1e-8, dtype=torch.float32, jitter: float = 0.1, progress=None, noise: str = "fixed", noise_prior=None,
-                   n_patients: Optional[int] = None) -> PopulationResult:
+                   n_patients: Optional[int] = None, initial_state=None) -> PopulationResult:
     """Sample the hierarchical population posterior of `model`'s mechanistic constants given the batch `data` (one row per
     patient; None with n_patients: the prior alone) with n_chains chains of HMC (`sampler="hmc"`, n_leapfrog steps) or NUTS
     (`sampler="nuts"`, max_tree_depth).  See the module docstring for the model.
@@ -363,7 +390,10 @@ def run_population(model, data: Optional[Dict[str, torch.Tensor]], num_samples: 
     tau_scale: the median tau0 of the between-patient sd, a scalar or name -> value (default: the prior's sd);
     tau_log_sd: the sd of log tau.  init: a fit_patients result for the same constants, or [B, K] values: the chains start at
     z_{b,k} = clip((theta_{b,k} - mu_pop_k) / tau0_k, +-3) instead of 0.  The observation model (noise_sigma, noise,
-    noise_prior), warm-up, thinning, seed, solver and `progress` are run_hmc's."""
+    noise_prior), warm-up, thinning, seed, solver and `progress` are run_hmc's.  initial_state: an InitialStatePrior
+    (inference/initial_state.py) makes the chosen components of every patient's initial state latent; the row is then
+    [ m | s | z | w ] with w from column K (B + 2), and the result's `initial_states()`, `predict` and `predictive_summary` pair
+    every draw with its own x0."""
     from inference.observation import ObservationModel
     if sampler not in ("hmc", "nuts"):
         raise ValueError(f"sampler must be 'hmc' or 'nuts', not {sampler!r}")
@@ -373,12 +403,19 @@ def run_population(model, data: Optional[Dict[str, torch.Tensor]], num_samples: 
     B = int(n_patients) if data is None else int(data["initial_state"].shape[0])
     _init_theta(init, names, B)
     ObservationModel(noise_sigma, noise, noise_prior)
+    hmc_cls, nuts_cls = _PopulationHmc, _PopulationNuts
+    if initial_state is not None:
+        from inference import initial_state as IS
+        IS._bind(initial_state, data, n_patients)
+        hmc_cls, nuts_cls = IS._pop_classes()
     kw = dict(noise_sigma=noise_sigma, ode_priors=ode_priors, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter,
               noise=noise, noise_prior=noise_prior, n_patients=n_patients, tau_scale=tau_scale, tau_log_sd=tau_log_sd, init=init)
+    if initial_state is not None:
+        kw["initial_state"] = initial_state
     made, solved = [], []
     if sampler == "hmc":
         def make():
-            made.append(_PopulationHmc(model, data, n_chains, **kw))
+            made.append(hmc_cls(model, data, n_chains, **kw))
             return made[0]
 
         def transition(s, it, warm, draws, stats, n_slots, slot):
@@ -390,7 +427,7 @@ def run_population(model, data: Optional[Dict[str, torch.Tensor]], num_samples: 
                             counts_message="num_samples, n_chains, n_leapfrog, thin must be >= 1 and num_warmup >= 0")
     else:
         def make():
-            made.append(_PopulationNuts(model, data, n_chains, max_tree_depth, **kw))
+            made.append(nuts_cls(model, data, n_chains, max_tree_depth, **kw))
             return made[0]
 
         def transition(s, it, warm, draws, stats, n_slots, slot):
@@ -405,4 +442,4 @@ def run_population(model, data: Optional[Dict[str, torch.Tensor]], num_samples: 
         res.stats["trajectories_solved"] = np.asarray(solved, dtype=np.int64)
     s = made[0]
     return PopulationResult(res.draws, s.pop_names, s.B, s.mu0.cpu(), s.sd0.cpu(), s.tau0.cpu(), s.omega, res.stats, model, s.ode_base,
-                            s.nn_base, s.om, data)
+                            s.nn_base, s.om, data, getattr(s, "lat", None))

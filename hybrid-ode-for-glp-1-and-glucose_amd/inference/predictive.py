@@ -450,7 +450,8 @@ def _rep_inputs(S, x0, t_span, external_inputs):
 
 def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None, n_bins: int = 10,
                        max_bytes: int = _DEFAULT_MAX_BYTES, solver: str = "dopri5", rtol: float = 1e-6, atol: float = 1e-8,
-                       dtype=torch.float32, *, quantiles=None, loo: bool = False, r_eff: float = 1.0) -> PredictiveSummary:
+                       dtype=torch.float32, *, quantiles=None, loo: bool = False, r_eff: float = 1.0,
+                       initial_states=None) -> PredictiveSummary:
     """The posterior-predictive summary of `draws` on `batch` {initial_state, time_points[, observations, observation_mask,
     external_inputs]}.  draws: a list of named parameter overrides (what `variational_params.sample` and `forward_param_sets`
     take), or a pair (nn_flat [S, P], ode_vec [S, 17]) of parameter tensors.  sigma: the observation noise, None, a scalar, six
@@ -459,7 +460,9 @@ def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None,
     piece of trajectories exists at a time, and the result does not depend on the cut.  quantiles (fractions in (0, 1), e.g.
     (0.025, 0.975) for the 95 % credible band): also the exact empirical quantiles of the LATENT trajectories across the draws,
     `PredictiveSummary.quantiles` / `.band()`; sigma does not enter them.  loo=True (needs observations and sigma): also PSIS-LOO
-    and WAIC of the pointwise log likelihood, `PredictiveSummary.loo`, with the relative efficiency r_eff of the draws."""
+    and WAIC of the pointwise log likelihood, `PredictiveSummary.loo`, with the relative efficiency r_eff of the draws.
+    initial_states [S, B, 6]: every draw's own initial states of the batch's patients (inference/initial_state.py) instead of
+    batch["initial_state"] under every draw."""
     if loo and sigma is None:
         raise ValueError("loo needs sigma: without observation noise there is no likelihood")
     from models.hybrid_ode_nn import _compute_device
@@ -474,6 +477,8 @@ def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None,
     acc = PredictiveAccumulator(B, T, batch.get("observations"), batch.get("observation_mask"), dtype, quantiles=quantiles,
                                 expected_draws=None if quantiles is None and not loo else max(S, 1), loo=loo, r_eff=r_eff)
     sig = acc._sigma(sigma, S)
+    if initial_states is not None and tuple(initial_states.shape) != (S, B, 6):
+        raise ValueError(f"initial_states must be [S, B, 6] = [{S}, {B}, 6], not {list(initial_states.shape)}")
     for lo, hi in cut_draws(S, B * T * 6 * 4, max_bytes):                         # (the solve's trajectories are fp32)
         n = hi - lo
         if named:
@@ -483,6 +488,8 @@ def predictive_summary(model, draws, batch: Dict[str, torch.Tensor], sigma=None,
             nn_flat = draws[0][lo:hi].to(dev, torch.float32).reshape(-1).contiguous()
             ode_vec = draws[1][lo:hi].to(dev, torch.float32).reshape(-1).contiguous()
         xs, ts, us = _rep_inputs(n, x0, t, batch.get("external_inputs"))
+        if initial_states is not None:
+            xs = initial_states[lo:hi].reshape(n * B, 6).to(x0.dtype)
         with torch.no_grad():
             y = model._solve(xs, ts, us, solver, rtol, atol, n_sets=n, nn_flat=nn_flat, ode_vec=ode_vec, differentiable=False)
         info = model.last_solve_info

@@ -417,7 +417,7 @@ def _rep(v, lo, hi, m):
     return v.repeat(m, *([1] * (v.dim() - 1))) if m > 1 else v
 
 
-def _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol, own_sets=False):
+def _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H, L, method, rtol, atol, own_sets=False, own_x0=False):
     """A likelihood of parameter sets (ode_vec, nn_flat) x the patients (x0, t, meal, tvns, gd: shared by the sets) and its
     gradient in one pass over the pieces of `plan` (_plan_sets): forward solve with tape (one tape buffer, handed from piece to
     piece) -> gy = cotangent(sol, s0, s1, lo, hi), the caller's likelihood of the sets s0..s1-1 x the patients lo..hi-1 at sol.y
@@ -428,11 +428,16 @@ def _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H,
     one row per (set, patient), the rows of the sets s0..s1-1 x the patients lo..hi-1 being the contiguous rows s G + lo ..; gode
     comes back with the same rows.  nn_flat is ONE network: it is replicated per piece into one buffer, sized for the largest
     piece and handed from piece to piece like the tape (trajectories of the piece x P reals), and gnn cannot be asked for.  The
-    plan's pieces hold at most OWN_SETS_MAX trajectories (_plan_sets(..., max_traj=OWN_SETS_MAX))."""
+    plan's pieces hold at most OWN_SETS_MAX trajectories (_plan_sets(..., max_traj=OWN_SETS_MAX)).
+
+    own_x0 (inference/initial_state.py): every (set, patient) has its own initial state.  x0 then holds [n_sets * G, 6], set-major;
+    a piece takes the rows s G + lo .. s G + hi of its sets, and gx0 comes back with the same rows, written per row instead of
+    summed over the sets.  t, meal, tvns and gd stay shared by the sets; own_sets combines with it."""
     steps, pieces = plan
     grads, one, n_sets = any(want), len(pieces) == 1, pieces[-1][1]
     P = hode.n_params(H, L)
-    G = x0.shape[0]
+    G = x0.shape[0] // n_sets if own_x0 else x0.shape[0]
+    x0_sets = x0.view(n_sets, G, 6) if own_x0 else None
     if own_sets and want[1]:
         raise ValueError("own_sets shares one network among the trajectories: there is no per-set network gradient")
     gx0 = torch.zeros_like(x0) if want[0] else None
@@ -450,7 +455,8 @@ def _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H,
             if nn_rep is None:
                 nn_rep = nn_flat.repeat(k)             # largest piece first: later ones fit
             nn_piece = nn_rep[:P * k]
-        args = (_rep(x0, lo, hi, m), t if t.dim() == 1 else _rep(t, lo, hi, m), _rep(meal, lo, hi, m), _rep(tvns, lo, hi, m),
+        x0_piece = x0_sets[s0:s1, lo:hi].reshape(-1, 6) if own_x0 else _rep(x0, lo, hi, m)
+        args = (x0_piece, t if t.dim() == 1 else _rep(t, lo, hi, m), _rep(meal, lo, hi, m), _rep(tvns, lo, hi, m),
                 _rep(gd, lo, hi, m), ode_vec[17 * r0:17 * r1], nn_piece, H, L)
         if not grads:
             cotangent(hode.solve_fwd(*args, method=method, rtol=rtol, atol=atol, n_sets=k), s0, s1, lo, hi)
@@ -458,7 +464,9 @@ def _run_sets(plan, cotangent, want, x0, t, meal, tvns, gd, ode_vec, nn_flat, H,
         sol = _solve_taped(*args, method, rtol, atol, k, steps, tape=tape, own_sets=own_sets)
         tape = sol.tape
         g0, gn, go = sol.backward(cotangent(sol, s0, s1, lo, hi), want_gnn=want[1], want_gode=want[2])
-        if gx0 is not None:
+        if gx0 is not None and own_x0:
+            gx0.view(n_sets, G, 6)[s0:s1, lo:hi] = g0.view(m, hi - lo, 6)
+        elif gx0 is not None:
             gx0[lo:hi] += g0.view(m, hi - lo, 6).sum(0)
         if one:
             gnn, gode = gn, go                     # (the whole batch in one launch: the adjoint's buffers ARE the result)

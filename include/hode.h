@@ -525,6 +525,36 @@ int hode_pop_grad_f32(void *stream, int A, int B, int K, int ld, const float *co
 int hode_pop_grad_f64(void *stream, int A, int B, int K, int ld, const double *coords, const double *gode, uint32_t ode_mask,
                       const double *sd0, const double *tau0, double tau_log_sd, double *glik);
 
+/* ---- Initial-state model (inference/initial_state.py; run_hmc / run_nuts / run_population with initial_state=...): a
+ *      reparameterisation layer between the samplers' chain coordinates and the solve's per-trajectory initial states.  B
+ *      patients, n_lat latent states (the set bits of lat_mask over the six states, ascending).  A row of coords [A][ld]
+ *      (DEVICE) holds from column `off` the B n_lat values w_{b,i} (patient-major, ld >= off + B n_lat), each with an N(0, 1)
+ *      prior.  m, s: fp64 [B][6], DEVICE; only the latent entries are read.  Everything is computed in double and rounded once.
+ *   - x0_params: x0_out[(a B + b) 6 + j] = m_{b,j} + s_{b,j} w_{b,rank(j)} (link 0) or m_{b,j} exp(s_{b,j} w_{b,rank(j)})
+ *     (link 1) for latent j, and x0_base[b 6 + j], copied exactly, otherwise.  With ode_p != NULL also the global constants of
+ *     the row, ode_p[a][17]: mu_k + sd_k coords[a ld + k] for the K set bits of ode_mask (ascending ODE index; mu, sd fp64 [K],
+ *     off >= K), ode_base[17] elsewhere.
+ *   - x0_grad: the transpose.  glik[a ld + off + b n_lat + i] = gx0[(a B + b) 6 + j] s_{b,j} (link 0) or
+ *     gx0[..] s_{b,j} x0_{b,j} (link 1, x0 recomputed in double from coords); with gode != NULL (the adjoint's per-row gradient
+ *     [A][17]) glik[a ld + k] = sd_k gode[a 17 + idx_k].  Values are written, not accumulated, and no other entry of glik is
+ *     touched (the pad, and the columns another layer owns: the pair composes with pop_params / pop_grad).
+ *   One lane per entry, no sums, no atomics: the same call gives the same bits.
+ *   HODE_EINVAL, nothing launched: A, B or n_lat < 1, n_lat > 6, popcount(lat_mask) != n_lat, K != popcount(ode_mask), K > 17,
+ *   link not 0 or 1, off < 0, off < K with ode_p / gode, ld < off + B n_lat, a NULL among the required pointers (coords, m, s,
+ *   x0_base, x0_out / gx0, glik; with ode_p: ode_base and, for K > 0, mu, sd; with gode and K > 0: sd). */
+int hode_x0_params_f32(void *stream, int A, int B, int n_lat, int ld, int off, const float *coords, uint32_t lat_mask, int link,
+                       const double *m, const double *s, const float *x0_base, float *x0_out, int K, uint32_t ode_mask,
+                       const double *mu, const double *sd, const float *ode_base, float *ode_p);
+int hode_x0_params_f64(void *stream, int A, int B, int n_lat, int ld, int off, const double *coords, uint32_t lat_mask, int link,
+                       const double *m, const double *s, const double *x0_base, double *x0_out, int K, uint32_t ode_mask,
+                       const double *mu, const double *sd, const double *ode_base, double *ode_p);
+int hode_x0_grad_f32(void *stream, int A, int B, int n_lat, int ld, int off, const float *coords, uint32_t lat_mask, int link,
+                     const double *m, const double *s, const float *gx0, int K, uint32_t ode_mask, const double *sd,
+                     const float *gode, float *glik);
+int hode_x0_grad_f64(void *stream, int A, int B, int n_lat, int ld, int off, const double *coords, uint32_t lat_mask, int link,
+                     const double *m, const double *s, const double *gx0, int K, uint32_t ode_mask, const double *sd,
+                     const double *gode, double *glik);
+
 /* =====================================================================================================
  * Sobol indices (inference/sobol.py, sobol_indices / sobol_study): the analysis half of the sensitivity study of the
  * reference's plots/plot_all.py:139-224, i.e. what SALib.analyze.sobol.analyze computes from the model outputs of a
