@@ -23,6 +23,10 @@ constexpr uint32_t kRngMomentum = 0, kRngAccept = 1, kRngJitter = 2, kRngInit = 
 constexpr uint32_t kRngNutsDir = 4, kRngNutsLeaf = 5, kRngNutsMerge = 6;
 // the bootstrap of the Sobol indices (hode_sobol.hip): resample r as the iteration, base sample q / 4 as the group, chain 0
 constexpr uint32_t kRngSobol = 7;
+// the particle filter (hode_filter.hip): the patient's key id0 + b as the chain, the filter step as the iteration.  Noise:
+// group 2 i + (j >> 2) gives particle i the normals of its states 4 (j >> 2) .. 4 (j >> 2) + 3; resampling: group 0, one
+// uniform per patient and step
+constexpr uint32_t kRngFilterNoise = 8, kRngFilterResample = 9;
 
 struct Philox4 { uint32_t x, y, z, w; };
 

@@ -33,7 +33,8 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_pred_tails_f32", "hode_pred_tails_f64", "hode_pred_quantiles_f32", "hode_pred_quantiles_f64",
            "hode_pred_loo_fold_f32", "hode_pred_loo_fold_f64", "hode_pred_loo_finish_f32", "hode_pred_loo_finish_f64",
            "hode_pop_params_f32", "hode_pop_params_f64", "hode_pop_grad_f32", "hode_pop_grad_f64",
-           "hode_x0_params_f32", "hode_x0_params_f64", "hode_x0_grad_f32", "hode_x0_grad_f64"]
+           "hode_x0_params_f32", "hode_x0_params_f64", "hode_x0_grad_f32", "hode_x0_grad_f64",
+           "hode_pf_step_f32", "hode_pf_step_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -446,6 +447,55 @@ def sobol_indices(Y, D, second_order=True, R=100, seed=0, conf_z=1.9599639845400
         C.c_int(int(R)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_double(conf_z), _ptr(out["S1"]), _ptr(out["ST"]), _ptr(out["S2"]),
         _ptr(out["S1_conf"]), _ptr(out["ST_conf"]), _ptr(out["S2_conf"]), _ptr(out["variance"])), "hode_sobol_indices")
     return out
+
+
+PF_MAX_PARTICLES, PF_MAX_AUX, PF_COLS = 4096, 17, 16
+PF_LINK = {"additive": 0, "log": 1}
+PF_STATS = ("log_evidence", "ess", "resampled", "alive")          # stats columns 0..3; 4..9 the means, 10..15 the variances
+
+
+def pf_step(x_in, obs, sigma, q, dt, lw, step, seed=0, id0=0, link=1, ess_frac=0.5, status=None, mask=None, aux_in=None, out=None):
+    """One step of the bootstrap particle filter (include/hode.h "Particle filter"): x_in [B, N, 6] fp32 or fp64 on the device,
+    obs [B, 6] (NaN = missing), mask uint8 [B, 6] or None, sigma / q fp64 [6] and dt fp64 [B] on the device, lw fp64 [B, N]
+    UPDATED IN PLACE, status int32 [B, N] or None, aux_in [B, N, n_aux] (n_aux <= 17) or None: a payload gathered with the particle.
+    `out`: (x_out, anc, stats, aux_out) buffers to write into (a loop reuses them), else they are allocated.
+    Returns (x_out [B, N, 6], anc int32 [B, N], stats fp64 [B, 16], aux_out or None)."""
+    _need_gpu(x_in)
+    if x_in.dim() != 3 or x_in.shape[2] != 6 or not x_in.is_contiguous():
+        raise HodeError("pf_step: x_in must be a contiguous [B, N, 6]")
+    B, N = int(x_in.shape[0]), int(x_in.shape[1])
+    dev, dt_ = x_in.device, x_in.dtype
+    if N > PF_MAX_PARTICLES:
+        raise HodeError(f"pf_step: N = {N} particles, the kernel takes up to {PF_MAX_PARTICLES} (HODE_PF_MAX_PARTICLES)")
+    obs = obs.to(device=dev, dtype=dt_).contiguous()
+    if obs.numel() != 6 * B:
+        raise HodeError("pf_step: obs must be [B, 6]")
+    for name, v, n in (("sigma", sigma, 6), ("q", q, 6), ("dt", dt, B), ("lw", lw, B * N)):
+        if v.dtype != torch.float64 or v.device != dev or v.numel() != n or not v.is_contiguous():
+            raise HodeError(f"pf_step: {name} must be a contiguous fp64 device tensor of {n} elements")
+    if mask is not None:
+        mask = mask.to(device=dev).contiguous()
+        if mask.dtype != torch.uint8 or mask.numel() != 6 * B:
+            raise HodeError("pf_step: mask must be uint8 [B, 6]")
+    if status is not None:
+        status = status.to(device=dev).contiguous()
+        if status.dtype != torch.int32 or status.numel() != B * N:
+            raise HodeError("pf_step: status must be int32 [B, N]")
+    n_aux = 0
+    if aux_in is not None:
+        if aux_in.dim() != 3 or tuple(aux_in.shape[:2]) != (B, N) or aux_in.dtype != dt_ or aux_in.device != dev or not aux_in.is_contiguous():
+            raise HodeError("pf_step: aux_in must be a contiguous [B, N, n_aux] of x_in's dtype")
+        n_aux = int(aux_in.shape[2])
+    if out is None:
+        out = (torch.empty_like(x_in), torch.empty(B, N, dtype=torch.int32, device=dev),
+               torch.empty(B, PF_COLS, dtype=torch.float64, device=dev), None if aux_in is None else torch.empty_like(aux_in))
+    x_out, anc, stats, aux_out = out
+    _check(getattr(load(), f"hode_pf_step_{_sfx(dt_)}")(
+        _stream(), C.c_int(B), C.c_int(N), C.c_uint32(int(step) & 0xFFFFFFFF), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+        C.c_uint32(int(id0) & 0xFFFFFFFF), _ptr(x_in), _ptr(status), _ptr(obs), _ptr(mask), _ptr(sigma), _ptr(q), _ptr(dt),
+        C.c_int(int(link)), C.c_double(float(ess_frac)), _ptr(lw), _ptr(x_out), _ptr(anc), _ptr(stats), C.c_int(n_aux), _ptr(aux_in),
+        _ptr(aux_out)), "hode_pf_step")
+    return x_out, anc, stats, aux_out
 
 
 PRED_MAX_BINS, PRED_FIXED_COLS, PRED_SCORE_BLOCKS = 32, 16, 128

@@ -797,6 +797,60 @@ int hode_pred_loo_finish_f64(void *stream, int64_t N, int K, double r_eff, const
                              const double *pmax, const double *psum, double *top, const double *rmax, const double *rsum, double *elpd_loo,
                              double *pareto_k, double *elpd_waic, double *p_waic, double *lppd, double *table, double *fit, double *work);
 
+/* =====================================================================================================
+ * Particle filter (inference/filter.py, run_filter): one step of a bootstrap particle filter per patient -- process noise,
+ * the weight update under the observation model, normalisation, effective sample size (ESS), systematic resampling and the
+ * gather -- i.e. everything between two forward solves of the B * N particle trajectories.
+ *
+ * Layout.  Patient-major: particle i of patient b is row b * N + i, 1 <= N <= HODE_PF_MAX_PARTICLES.  One workgroup of 256
+ * lanes per patient; the patient's N cumulative weights (fp64) live in LDS, 32 KB at the maximum.
+ *
+ * Arguments (DEVICE unless noted): B, N, step, seed, id0, link, ess_frac, n_aux on the host; patient b draws from the Philox
+ * key id0 + b (the samplers' generator: key = (seed bits 0..31, id0 + b), counter = (group, tag, step, seed bits 32..63));
+ * x_in [B*N][6] the solve's output row at this time; status [B*N] int32 or NULL; obs [B][6]; mask [B][6] uint8 or NULL;
+ * sigma [6], q [6], dt [B] fp64; lw [B*N] fp64 IN/OUT, the unnormalised log-weights; x_out [B*N][6]; anc [B*N] int32;
+ * stats [B][HODE_PF_COLS] fp64; aux_in / aux_out [B*N][n_aux], 0 <= n_aux <= HODE_PF_MAX_AUX, a payload that is gathered
+ * with the particle (run_filter carries each particle's 17 mechanistic constants in it; both NULL with n_aux == 0).
+ *
+ * Everything below is computed in fp64 and rounded once on store.
+ *  a. Noise.  For state j with s = q_j sqrt(dt_b) > 0: xi = element j & 3 of the four normals (Box-Muller, as the samplers')
+ *     of the block (group 2 i + (j >> 2), tag 8, step); link HODE_PF_LINK_ADD: x += s xi; HODE_PF_LINK_LOG:
+ *     x *= exp(s xi - s^2 / 2).  With s == 0 the state is copied exactly.
+ *  b. Weight.  lw_i += sum_j seen_j [-((obs_j - x_ij) / sigma_j)^2 / 2 - log sigma_j - log(2 pi) / 2]; seen_j: obs_j finite and,
+ *     with a mask, the mask byte set (no arithmetic touches an unseen obs_j).  A particle with status != 0, a non-finite state,
+ *     or lw = -inf (or NaN) on entry gets lw = -inf: it is dead and stays dead.
+ *  c. Normalise.  m = max lw, w_i = exp(lw_i - m), c_k = sum_{i <= k} w_i.  stats: [0] the log-evidence increment
+ *     m + log c_{N-1} - (m_in + log c_in), the _in values being the same quantities of the log-weights on entry;
+ *     [1] ESS = (sum w)^2 / sum w^2; [3] particles alive; [4..9] the weighted mean of each state; [10..15] the weighted variance
+ *     of each state about that mean.  No particle alive: increment -inf, ESS 0, mean and variance NaN, x_out = x after (a),
+ *     anc = identity, lw stays -inf.
+ *  d. Resample iff ESS < ess_frac * N; stats[2] = 1 then, else 0.  Systematic: one u in (0, 1) per patient and step (word x of
+ *     the block (group 0, tag 9, step)), anc_i = min{k : c_k >= (i + u) / N * c_{N-1}}, never a dead particle; then lw = 0 in
+ *     every slot.  Otherwise anc = identity and lw is kept.
+ *  e. Gather.  x_out[i] = x[anc_i] after (a), aux_out[i] = aux_in[anc_i].  x_out may not alias x_in, aux_out not aux_in.
+ *
+ * Reductions run in a fixed order and there are no floating-point atomics: the same call gives the same bits, and a patient's
+ * result depends on its key id0 + b only, not on B or on its row.  c_k comes from a parallel scan: against a sequential sum,
+ * anc can differ only where a pointer falls within the summation error of a boundary c_k.
+ *
+ * HODE_EINVAL (nothing launched): B < 1, N < 1, n_aux outside 0..HODE_PF_MAX_AUX, link not 0 or 1, ess_frac outside [0, 1] or
+ * NaN, a NULL among x_in, obs, sigma, q, dt, lw, x_out, anc, stats (and, with n_aux > 0, aux_in, aux_out), x_out == x_in,
+ * aux_out == aux_in.  HODE_EUNSUPPORTED: N > HODE_PF_MAX_PARTICLES (a bad argument outranks it).
+ * ===================================================================================================== */
+#define HODE_PF_MAX_PARTICLES 4096
+#define HODE_PF_MAX_AUX 17
+#define HODE_PF_COLS 16
+#define HODE_PF_LINK_ADD 0
+#define HODE_PF_LINK_LOG 1
+int hode_pf_step_f32(void *stream, int B, int N, uint32_t step, uint64_t seed, uint32_t id0, const float *x_in, const int32_t *status,
+                     const float *obs, const uint8_t *mask, const double *sigma, const double *q, const double *dt, int link,
+                     double ess_frac, double *lw, float *x_out, int32_t *anc, double *stats, int n_aux, const float *aux_in,
+                     float *aux_out);
+int hode_pf_step_f64(void *stream, int B, int N, uint32_t step, uint64_t seed, uint32_t id0, const double *x_in, const int32_t *status,
+                     const double *obs, const uint8_t *mask, const double *sigma, const double *q, const double *dt, int link,
+                     double ess_frac, double *lw, double *x_out, int32_t *anc, double *stats, int n_aux, const double *aux_in,
+                     double *aux_out);
+
 #ifdef __cplusplus
 }
 #endif
