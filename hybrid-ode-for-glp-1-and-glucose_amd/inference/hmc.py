@@ -11,7 +11,13 @@ Static-trajectory HMC with C independent chains: each leapfrog step is ONE forwa
 C x N trajectories (the C positions ride in the kernels' parameter-set dimension), the per-chain sum of squares and its
 cotangent come from hode_mse_sets, and everything else a step does to the chains (momentum, kicks, drifts, the Metropolis
 test, dual averaging, draws, the mass matrix) is a HIP kernel of csrc/hode_hmc.hip.  Step sizes are per chain (dual
-averaging, Stan's constants), the diagonal mass matrix is pooled across chains over Stan's doubling warm-up windows."""
+averaging, Stan's constants), the diagonal mass matrix is pooled across chains over Stan's doubling warm-up windows.
+
+Two things are kept apart.  What a chain's D coordinates mean is a target: `_PlainTarget` here (the density above),
+inference/population.py's and inference/initial_state.py's for the other posteriors.  How chains move is `_Sampler` (and
+inference/nuts.py's `_NutsSampler`, the same plus the tree state), which is handed a target and never subclassed per posterior.
+`_run_schedule` is the one driver of run_hmc, run_nuts and run_population: the warm-up schedule around the HMC or the NUTS
+transition."""
 import math
 from functools import partial
 from typing import Dict, Optional, Tuple
@@ -51,16 +57,85 @@ def _windows(num_warmup):
     return init, out
 
 
+def _parse_priors(ode_priors):
+    """A prior dictionary name -> (mean, sd) (None: the reference's) -> (names in ascending ODE-index order, their bit mask, mu, sd
+    as float lists) after the unknown-name and sd > 0 checks; no device is touched."""
+    from models.ode_core import ODE_PARAM_NAMES
+    priors = dict(REFERENCE_PRIORS if ode_priors is None else ode_priors)
+    for k in priors:
+        if k not in ODE_PARAM_NAMES:
+            raise ValueError(f"unknown mechanistic constant {k!r}; known: {list(ODE_PARAM_NAMES)}")
+    names = [n for n in ODE_PARAM_NAMES if n in priors]
+    mu, sd = [float(priors[n][0]) for n in names], [float(priors[n][1]) for n in names]
+    if names and not min(sd) > 0.0:
+        raise ValueError("the prior sd of every constant must be > 0")
+    return names, sum(1 << ODE_PARAM_NAMES.index(n) for n in names), mu, sd
+
+
+def _jitter_all(s):
+    """The start + 0.1 N(0, 1) on every coordinate (the chain's own normals)."""
+    s.refresh(_INIT_ITER, 0.0)
+    s.z[:, :s.D].add_(s.p[:, :s.D], alpha=0.1)
+
+
+class _PlainTarget:
+    """What a chain's D coordinates mean, for run_hmc / run_nuts: the sampled constants in prior-standardised units, then (with
+    sample_nn) the P weights.  A target knows nothing of HMC or NUTS.  Its constructor is the host-side validation (no device, no
+    model); `layout(s)` gives the sampler s what the chain kernels see (D, P, ode_names, ode_mask, n_ode, sample_nn, nn_names, mu,
+    sd), `start(s)` its parameter buffers and -> z [C, ld], `initial_jitter(s)` moves z off the start, and `evaluate(s, A)` maps
+    the first A rows of coordinates to parameters, runs the pieces and leaves gnn / gode / status / loss_sum for the chain
+    kernels.  inference/population.py and inference/initial_state.py hold the other two targets."""
+
+    def __init__(self, ode_priors=None, sample_nn=True):
+        self.names, self.mask, self.mu, self.sd = _parse_priors(ode_priors)
+        self.sample_nn = bool(sample_nn)
+        if not self.names and not self.sample_nn:
+            raise ValueError("nothing to sample: no ode_priors and sample_nn=False")
+
+    def layout(self, s):
+        f64 = dict(dtype=torch.float64, device=s.dev)
+        s.P = hode.n_params(s.H, s.L)
+        s.ode_names, s.ode_mask, s.n_ode, s.sample_nn = self.names, self.mask, len(self.names), self.sample_nn   # ascending ODE index = z order
+        s.nn_names = [(n, tuple(p.shape)) for n, p in s.model.nn_residual.named_parameters()]
+        s.D = s.n_ode + (s.P if s.sample_nn else 0)
+        s.mu, s.sd = torch.tensor(self.mu or [0.0], **f64), torch.tensor(self.sd or [1.0], **f64)
+
+    def start(self, s):
+        """The chains' parameter buffers nn_p / ode_p and -> z [C, ld] at the model's own parameters."""
+        from models.ode_core import ODE_PARAM_NAMES
+        s.nn_p = s.nn_base.repeat(s.C).contiguous()
+        s.ode_p = s.ode_base.repeat(s.C).contiguous()
+        z = torch.zeros(s.C, s.ld, dtype=s.dt, device=s.dev)
+        for i, n in enumerate(s.ode_names):
+            z[:, i] = (float(s.ode_base[ODE_PARAM_NAMES.index(n)]) - float(s.mu[i])) / float(s.sd[i])
+        if s.sample_nn:
+            z[:, s.n_ode:s.D] = s.nn_base
+        return z
+
+    def initial_jitter(self, s):
+        """The reference's start (mcmc.py:101-113): MLP weights + 0.01 N(0,1); sampled constants + 0.1 sd N(0,1)."""
+        s.refresh(_INIT_ITER, 0.0)                    # p = xi (minv = 1): the chain's own normals
+        scale = torch.full((s.ld,), 0.01, dtype=s.dt, device=s.dev)
+        scale[:s.n_ode] = 0.1
+        scale[s.D:] = 0
+        s.z.addcmul_(s.p, scale)
+
+    def evaluate(self, s, A):
+        """Forward with tape -> hode_mse_sets (or hode_obs_nll_sets: the negative log-likelihood of the observation model) ->
+        adjoint at the parameters in nn_p / ode_p, piece by piece under the tape budget."""
+        _, s.gnn, s.gode = s._run_pieces(A, (False, s.sample_nn, s.n_ode > 0), x0=s.x0, ode_vec=s.ode_p, nn_flat=s.nn_p)
+
+
 class _Sampler:
-    """Device state of C chains and the three passes of an iteration (refresh, L leapfrog steps, accept).  Tests drive it
-    directly; run_hmc is the schedule around it."""
+    """Device state of C chains and the three passes of an iteration (refresh, L leapfrog steps, accept) over a target (default:
+    the _PlainTarget of ode_priors / sample_nn).  Tests drive it directly; run_hmc is the schedule around it."""
 
     def __init__(self, model, data, n_chains, noise_sigma=1.0, ode_priors=None, sample_nn=True, seed=0, solver="dopri5",
-                 rtol=1e-6, atol=1e-8, dtype=torch.float32, jitter=0.1, noise="fixed", noise_prior=None):
+                 rtol=1e-6, atol=1e-8, dtype=torch.float32, jitter=0.1, noise="fixed", noise_prior=None, target=None):
         from inference.observation import ObservationModel
         from models.hybrid_ode_nn import _compute_device, _device_batch, _method
-        from models.ode_core import ODE_PARAM_NAMES
         self.om = ObservationModel(noise_sigma, noise, noise_prior)          # validates before any device is needed
+        self.target = _PlainTarget(ode_priors, sample_nn) if target is None else target          # ... and so did the target
         model._check_supported()
         self.model, self.dt = model, dtype
         dev = self.dev = _compute_device()
@@ -71,12 +146,12 @@ class _Sampler:
         C = self.C = int(n_chains)
         f64 = dict(dtype=torch.float64, device=dev)
         R = dict(dtype=dtype, device=dev)
-        self._layout(ode_priors, sample_nn)
+        self.target.layout(self)
         self.ld = (self.D + 3) // 4 * 4
         with torch.no_grad():
             nn0, ode0 = model._params_on(dev)
         self.nn_base, self.ode_base = nn0.detach().to(dtype).contiguous(), ode0.detach().to(dtype).contiguous()
-        z = self._start()
+        z = self.target.start(self)
         self.z, self.p, self.g = z, torch.zeros(C, self.ld, **R), torch.zeros(C, self.ld, **R)
         self.z0, self.g0 = torch.zeros_like(z), torch.zeros_like(z)
         self.minv = torch.ones(self.ld, **R)
@@ -104,60 +179,27 @@ class _Sampler:
                 self.lik_scale = 1.0
                 self.sse = torch.zeros(C, 6, **f64)
             self.status = torch.zeros(C, self.N, dtype=torch.int32, device=dev)
-            self.solve_args = (self.x0, self.t, self.meal, self.tvns, self.gd, self.ode_p, self.nn_p, self.H, self.L, self.method,
-                               self.rtol, self.atol)          # what _run_sets takes: the batch and the chains' parameter buffers
         self.gnn = self.gode = None
-
-    # ------------------------------------------------------------------ the coordinate layout (inference/population.py replaces it)
-    def _layout(self, ode_priors, sample_nn):
-        """What a chain's D coordinates are: the sampled constants (names, mask, prior mu / sd) and, with sample_nn, the P weights."""
-        from models.ode_core import ODE_PARAM_NAMES
-        self.P = hode.n_params(self.H, self.L)
-        priors = dict(REFERENCE_PRIORS if ode_priors is None else ode_priors)
-        for k in priors:
-            if k not in ODE_PARAM_NAMES:
-                raise ValueError(f"unknown mechanistic constant {k!r}; known: {list(ODE_PARAM_NAMES)}")
-        self.ode_names = [n for n in ODE_PARAM_NAMES if n in priors]           # ascending ODE index = z order
-        self.ode_mask = sum(1 << ODE_PARAM_NAMES.index(n) for n in self.ode_names)
-        self.n_ode, self.sample_nn = len(self.ode_names), bool(sample_nn)
-        self.nn_names = [(n, tuple(p.shape)) for n, p in self.model.nn_residual.named_parameters()]
-        self.D = self.n_ode + (self.P if self.sample_nn else 0)
-        if self.D == 0:
-            raise ValueError("nothing to sample: no ode_priors and sample_nn=False")
-        f64 = dict(dtype=torch.float64, device=self.dev)
-        self.mu = torch.tensor([float(priors[n][0]) for n in self.ode_names] or [0.0], **f64)
-        self.sd = torch.tensor([float(priors[n][1]) for n in self.ode_names] or [1.0], **f64)
-
-    def _start(self):
-        """The chains' parameter buffers nn_p / ode_p and -> z [C, ld] at the model's own parameters."""
-        from models.ode_core import ODE_PARAM_NAMES
-        C = self.C
-        self.nn_p = self.nn_base.repeat(C).contiguous()
-        self.ode_p = self.ode_base.repeat(C).contiguous()
-        z = torch.zeros(C, self.ld, dtype=self.dt, device=self.dev)
-        for i, n in enumerate(self.ode_names):
-            z[:, i] = (float(self.ode_base[ODE_PARAM_NAMES.index(n)]) - float(self.mu[i])) / float(self.sd[i])
-        if self.sample_nn:
-            z[:, self.n_ode:self.D] = self.nn_base
-        return z
 
     # ------------------------------------------------------------------ the pieces of an iteration
     def evaluate(self, n_sets=None):
-        """Likelihood sum of squares, its gradient and the solve statuses at the parameters in nn_p / ode_p: of all chains, or
-        of the first n_sets parameter sets (the NUTS driver's compacted active chains); forward with tape -> hode_mse_sets (or
-        hode_obs_nll_sets: the negative log-likelihood of the observation model) -> adjoint, piece by piece under the tape
-        budget (models.hybrid_ode_nn._run_sets; this class supplies the cotangent of a piece)."""
-        if not self.has_data:
-            return
-        _, self.gnn, self.gode = self._run_pieces(self.C if n_sets is None else int(n_sets), (False, self.sample_nn, self.n_ode > 0))
+        """Likelihood sum of squares, its gradient and the solve statuses at the chains' coordinates, as the target maps them to
+        parameters: of all chains, or of the first n_sets parameter sets (the NUTS driver's compacted active chains)."""
+        if self.has_data:
+            self.target.evaluate(self, self.C if n_sets is None else int(n_sets))
 
-    def _run_pieces(self, C, want, max_traj=None, **run_kw):
-        """loss_sum, the statuses and the gradients `want` of the first C chains over the pieces of the plan; max_traj and run_kw
-        go to _plan_sets and _run_sets (own_sets: inference/population.py)."""
+    def initial_jitter(self):
+        self.target.initial_jitter(self)
+
+    def _run_pieces(self, C, want, *, x0, ode_vec, nn_flat, max_traj=None, **run_kw):
+        """loss_sum, the statuses and the gradients `want` of the first C chains over the pieces of the plan
+        (models.hybrid_ode_nn._run_sets; this class supplies the cotangent of a piece).  The target names what the pieces solve:
+        the x0 rows, the constants and the network vector; max_traj and run_kw go to _plan_sets and _run_sets (own_sets, own_x0)."""
         import models.hybrid_ode_nn as HN
         N = self.N
         plan = HN._plan_sets(self.dev, C, N, self.T, self.method, self.x0.element_size(), self.L, self.H, self.model.tape_steps,
                              max_traj=max_traj)
+        solve = (x0, self.t, self.meal, self.tvns, self.gd, ode_vec, nn_flat, self.H, self.L, self.method, self.rtol, self.atol)
         lo, hi = plan[1][0][2:]
         self.loss_sum.zero_()
         stat = []
@@ -167,11 +209,10 @@ class _Sampler:
             flags = 0
             if self.om.marginal and hi - lo < N:
                 # a set cut into pieces: its cotangent needs the sums of the WHOLE set, so the pieces run once without a tape first
-                HN._run_sets(plan, partial(self._obs_piece, [], hode.capi.OBS_SUMS_ONLY), (False, False, False), *self.solve_args,
-                             **run_kw)
+                HN._run_sets(plan, partial(self._obs_piece, [], hode.capi.OBS_SUMS_ONLY), (False, False, False), *solve, **run_kw)
                 flags = hode.capi.OBS_FROM_SSE
             cotangent = partial(self._obs_piece, stat, flags)
-        out = HN._run_sets(plan, cotangent, want, *self.solve_args, **run_kw)
+        out = HN._run_sets(plan, cotangent, want, *solve, **run_kw)
         self.status = (stat[0] if len(stat) == 1 else torch.cat(stat)).view(C, N)
         return out
 
@@ -218,14 +259,6 @@ class _Sampler:
         self.evaluate()
         self.failed.zero_()
         self.leapfrog(hode.capi.HMC_ASSEMBLE)
-
-    def initial_jitter(self):
-        """The reference's start (mcmc.py:101-113): MLP weights + 0.01 N(0,1); sampled constants + 0.1 sd N(0,1)."""
-        self.refresh(_INIT_ITER, 0.0)                 # p = xi (minv = 1): the chain's own normals
-        scale = torch.full((self.ld,), 0.01, dtype=self.dt, device=self.dev)
-        scale[:self.n_ode] = 0.1
-        scale[self.D:] = 0
-        self.z.addcmul_(self.p, scale)
 
     def find_step_size(self, window):
         """Stan's initial step-size heuristic for every chain at once: one trial = one leapfrog step of all chains, at most
@@ -494,41 +527,56 @@ def run_hmc(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 1
 
     initial_state: an `inference.initial_state.InitialStatePrior` makes the chosen components of every patient's initial state
     latent (sample_nn must be False; ode_priors={} samples the states alone; data=None needs n_patients) -> LatentStateResult."""
-    if initial_state is not None:
-        from inference.initial_state import _run_latent
-        return _run_latent("hmc", model, data, initial_state, num_samples=num_samples, num_warmup=num_warmup, n_chains=n_chains,
-                           n_leapfrog=n_leapfrog, target_accept=target_accept, noise_sigma=noise_sigma, ode_priors=ode_priors,
-                           sample_nn=sample_nn, thin=thin, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter,
-                           progress=progress, noise=noise, noise_prior=noise_prior, n_patients=n_patients)
-
-    def transition(s, it, warm, draws, stats, n_slots, slot):
-        s.refresh(it)
-        s.trajectory(n_leapfrog)
-        s.accept(hode.capi.HMC_ADAPT if warm else hode.capi.HMC_SAMPLE, it, target_accept, draws, stats, n_slots, slot)
-    return _run_schedule(lambda: _Sampler(model, data, n_chains, noise_sigma, ode_priors, sample_nn, seed, solver, rtol, atol, dtype,
-                                          jitter, noise, noise_prior),
-                         transition, n_stats=4, num_samples=num_samples, num_warmup=num_warmup, thin=thin, target_accept=target_accept,
-                         progress=progress, counts_ok=min(num_samples, n_chains, n_leapfrog, thin) >= 1,
-                         counts_message="num_samples, n_chains, n_leapfrog, thin must be >= 1 and num_warmup >= 0")
+    return _run("hmc", model, data, initial_state, n_patients, ode_priors, sample_nn, n_chains=n_chains, n_leapfrog=n_leapfrog,
+                num_samples=num_samples, num_warmup=num_warmup, thin=thin, target_accept=target_accept, progress=progress,
+                noise_sigma=noise_sigma, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter, noise=noise,
+                noise_prior=noise_prior)
 
 
-def _run_schedule(make_sampler, transition, *, n_stats, num_samples, num_warmup, thin, target_accept, progress, counts_ok, counts_message,
-                  extra_stats=None, extra_progress=None):
-    """What run_hmc and run_nuts share: the argument checks (`counts_ok`: the sampler's counts are all >= 1, else ValueError
-    `counts_message`), the sampler of `make_sampler()`, Stan's warm-up schedule and the sampling iterations around
-    `transition(s, it, warm, draws, stats, n_slots, slot)` -- one iteration of all chains that adapts (warm) or records into
-    slot `slot` of draws / stats [C, n_slots, n_stats] (-1: not kept) -- and the result.  `extra_stats(stats array) -> dict`
-    names the sampler's own stat columns, `extra_progress(s) -> dict` adds its entries to what `progress` is told."""
-    if not counts_ok or num_warmup < 0:
-        raise ValueError(counts_message)
+def _run(kind, model, data, initial_state, n_patients, ode_priors, sample_nn, **kw):
+    """run_hmc (kind "hmc") and run_nuts ("nuts"): the plain target -> HMCResult, or with initial_state the latent one ->
+    LatentStateResult; kw goes to _run_schedule."""
+    if initial_state is None:
+        s, draws, stats = _run_schedule(kind, model, data, ode_priors=ode_priors, sample_nn=sample_nn, **kw)
+        return HMCResult(draws, s.ode_names, s.nn_names if s.sample_nn else [], stats, s.model, s.ode_base, s.nn_base, s.om, s.data)
+    from inference.initial_state import LatentStateResult, _LatentTarget
+    t = _LatentTarget(initial_state, data, n_patients, ode_priors=ode_priors, sample_nn=sample_nn)
+    s, draws, stats = _run_schedule(kind, model, data, target=t, **kw)
+    return LatentStateResult(draws, t.g_names, t.g_mu.cpu(), t.g_sd.cpu(), t.lat, stats, model, s.ode_base, s.nn_base, s.om, data)
+
+
+def _run_schedule(kind, model, data, *, n_chains, num_samples, num_warmup, thin, target_accept, progress, n_leapfrog=16, max_tree_depth=10,
+                  **sampler_kw):
+    """The one driver of every entry point: the argument checks of the counts, the sampler of `kind` ("hmc": _Sampler, "nuts":
+    _NutsSampler; sampler_kw holds its target and observation model), Stan's warm-up schedule and the sampling iterations around
+    the kind's transition -- one iteration of all chains that adapts (warm) or records into slot `slot` of draws / stats
+    [C, n_slots, n_stats] (-1: not kept).  -> (the sampler, draws, the stats dictionary); NUTS adds tree_depth, n_leapfrog and
+    trajectories_solved [iterations] to it and leaf_steps to what `progress` is told."""
+    nuts = kind == "nuts"
+    if min(num_samples, n_chains, thin, 1 if nuts else n_leapfrog) < 1 or num_warmup < 0:
+        raise ValueError(f"num_samples, n_chains, {'' if nuts else 'n_leapfrog, '}thin must be >= 1 and num_warmup >= 0")
     if not 0.0 < target_accept < 1.0:
         raise ValueError("target_accept must lie in (0, 1)")
-    s = make_sampler()
+    cap, solved = hode.capi, []
+    if nuts:
+        from inference.nuts import _NutsSampler
+        s = _NutsSampler(model, data, n_chains, max_tree_depth, **sampler_kw)
+
+        def transition(it, warm, slot):
+            s.transition(it)
+            s.finish(warm, target_accept, draws, stats, n_slots, slot)
+            solved.append(s.solved)
+    else:
+        s = _Sampler(model, data, n_chains, **sampler_kw)
+
+        def transition(it, warm, slot):
+            s.refresh(it)
+            s.trajectory(n_leapfrog)
+            s.accept(cap.HMC_ADAPT if warm else cap.HMC_SAMPLE, it, target_accept, draws, stats, n_slots, slot)
     C, D = s.C, s.D
     n_slots = (num_samples + thin - 1) // thin
     draws = torch.empty(C, n_slots, D, dtype=s.dt, device=s.dev)
-    stats = torch.empty(C, n_slots, n_stats, dtype=torch.float64, device=s.dev)
-    cap = hode.capi
+    stats = torch.empty(C, n_slots, 6 if nuts else 4, dtype=torch.float64, device=s.dev)
     s.initial_jitter()
     s.gradient()
     window = 0
@@ -540,7 +588,7 @@ def _run_schedule(make_sampler, transition, *, n_stats, num_samples, num_warmup,
         slot = -1
         if not warm and (it - num_warmup) % thin == 0:
             slot = (it - num_warmup) // thin
-        transition(s, it, warm, draws, stats, n_slots, slot)
+        transition(it, warm, slot)
         if warm and any(a <= it < b for a, b in wins):
             s.welford(cap.HMC_WELFORD_ACCUM)
         if warm and (it + 1) in ends:
@@ -550,10 +598,12 @@ def _run_schedule(make_sampler, transition, *, n_stats, num_samples, num_warmup,
         if warm and it + 1 == num_warmup:
             s.accept(cap.HMC_DA_FINISH, it)
         if progress is not None:
-            progress(it, {"step_size": s.log_eps.exp().mean().item(), **(extra_progress(s) if extra_progress else {})})
+            progress(it, {"step_size": s.log_eps.exp().mean().item(), **({"leaf_steps": s.leaf_steps} if nuts else {})})
     st = stats.cpu().numpy()
     out = {"accept_prob": st[..., 0], "log_posterior": st[..., 1], "divergent": st[..., 2] > 0, "failed_solve": st[..., 3] > 0}
-    out.update(extra_stats(st) if extra_stats else {})
+    if nuts:
+        out.update(tree_depth=st[..., 4].astype(np.int64), n_leapfrog=st[..., 5].astype(np.int64))
     out.update(step_size=s.log_eps.exp().cpu().numpy(), inv_mass=s.minv[:D].double().cpu().numpy())
-    return HMCResult(draws, s.ode_names, s.nn_names if s.sample_nn else [], out, s.model, s.ode_base, s.nn_base, s.om,
-                     s.data)
+    if nuts:
+        out["trajectories_solved"] = np.asarray(solved, dtype=np.int64)
+    return s, draws, out

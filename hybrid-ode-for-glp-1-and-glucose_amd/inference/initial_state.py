@@ -13,7 +13,8 @@ likelihood term of the latent state.  The prior must therefore NOT be "the first
 the first observation twice.  Take it from knowledge that does not come from this record's first row, e.g. the cohort
 (`InitialStatePrior.from_batch`) or the physiological range.
 
-The layer sits between the unchanged sampler kernels and the solve, as inference/population.py does: hode_x0_params maps the
+The layer sits between the unchanged sampler kernels and the solve, as inference/population.py does -- the target `_LatentTarget`,
+alone or in front of the population's: hode_x0_params maps the
 chain coordinates to one initial state per (chain, patient), hode_x0_grad takes the adjoint's per-trajectory gx0 back
 (csrc/hode_x0.hip).  A coordinate row is [ z_ode (K) | w (B n_lat) ] for run_hmc / run_nuts, the network at the model's weights,
 and [ m | s | z | w ] with w from column K (B + 2) for run_population.  The sampler kernels see n_ode = 0 and P = D "weights"
@@ -24,8 +25,7 @@ import numpy as np
 import torch
 
 import hode
-from inference.hmc import HMCResult, _INIT_ITER, _run_schedule, _Sampler
-from inference.nuts import _NutsSampler
+from inference.hmc import HMCResult, _jitter_all, _parse_priors
 
 __all__ = ["InitialStatePrior", "LatentStateResult", "STATE_NAMES"]
 
@@ -185,128 +185,78 @@ def _bind(initial_state, data, n_patients) -> _BoundPrior:
     return initial_state.bind(x0.shape[0], x0)
 
 
-# ---------------------------------------------------------------------------------------------------- sampler
-class _LatentState:
-    """Mixin over _Sampler / _NutsSampler, or over inference.population._Population in front of either: the coordinate layout, the
-    start point and `evaluate` with a latent initial state; everything else is inherited."""
+# ---------------------------------------------------------------------------------------------------- target
+class _LatentTarget:
+    """Latent initial states as a sampler target (inference.hmc._PlainTarget states the protocol).  `inner` is None: the row is
+    [ z_ode (g_K) | w ] and this target carries the constants itself (g_names / g_mask / g_mu / g_sd; hode_x0_params and
+    hode_x0_grad do both maps).  `inner` is the population target: the row is its row, then w, and this target stands in front
+    of it.  The two are two code paths because the kernels fuse differently; `off` is where w starts in either."""
 
-    def __init__(self, model, data, n_chains, *args, initial_state=None, n_patients=None, **kw):
-        from inference.population import _Population
-        self._pop = isinstance(self, _Population)
-        self.lat = _bind(initial_state, data, n_patients)
-        if kw.get("sample_nn") and not self._pop:
+    def __init__(self, initial_state, data, n_patients=None, ode_priors=None, sample_nn=False, inner=None):
+        if sample_nn:
             raise ValueError("sample_nn=True cannot be combined with initial_state: the network stays at the model's weights "
-                             "(the sampler kernels take no coordinates beyond n_ode + P)")
-        kw.pop("sample_nn", None)
-        if self._pop:
-            kw["n_patients"] = n_patients
-        super().__init__(model, data, n_chains, *args, sample_nn=True, **kw)
-        if self.has_data and not self._pop:      # the pieces take the chains' constants and one copy of the network per chain
-            self.solve_args = self.solve_args[:5] + (self.ode_p, self.nn_rep) + self.solve_args[7:]
+                             "(the sampler kernels take no coordinates beyond n_ode + P); pass sample_nn=False")
+        self.inner = inner
+        self.lat = _bind(initial_state, data, n_patients)
+        self.g_names, self.g_mask, self._mu, self._sd = ([], 0, [], []) if inner is not None else _parse_priors(ode_priors)
+        self.g_K = len(self.g_names)                                             # K = 0: state estimation at fixed constants
 
-    def _layout(self, ode_priors, sample_nn):
-        f64 = dict(dtype=torch.float64, device=self.dev)
+    def layout(self, s):
+        f64 = dict(dtype=torch.float64, device=s.dev)
         lat = self.lat
-        if self._pop:
-            super()._layout(ode_priors, sample_nn)
-            self.g_K, self.g_mask, self.g_names = 0, 0, []
+        if self.inner is not None:
+            self.inner.layout(s)
             self.g_mu = self.g_sd = None
         else:
-            from inference.hmc import REFERENCE_PRIORS
-            from models.ode_core import ODE_PARAM_NAMES
-            self.B = lat.B
-            priors = dict(REFERENCE_PRIORS if ode_priors is None else ode_priors)
-            for k in priors:
-                if k not in ODE_PARAM_NAMES:
-                    raise ValueError(f"unknown mechanistic constant {k!r}; known: {list(ODE_PARAM_NAMES)}")
-            self.g_names = [n for n in ODE_PARAM_NAMES if n in priors]           # ascending ODE index = coordinate order
-            self.g_mask = sum(1 << ODE_PARAM_NAMES.index(n) for n in self.g_names)
-            self.g_K = len(self.g_names)                                         # K = 0: state estimation at fixed constants
-            self.g_mu = torch.tensor([float(priors[n][0]) for n in self.g_names] or [0.0], **f64)
-            self.g_sd = torch.tensor([float(priors[n][1]) for n in self.g_names] or [1.0], **f64)
-            if self.g_K and float(self.g_sd.min()) <= 0.0:
-                raise ValueError("the prior sd of every constant must be > 0")
+            self.g_mu, self.g_sd = torch.tensor(self._mu or [0.0], **f64), torch.tensor(self._sd or [1.0], **f64)
             # what the sampler kernels see: no constants of their own, D = P "weights" whose buffer is the coordinate scratch
-            self.ode_names, self.ode_mask, self.n_ode, self.sample_nn, self.nn_names = [], 0, 0, True, []
-            self.D = self.P = self.g_K
-            self.mu, self.sd = torch.tensor([0.0], **f64), torch.tensor([1.0], **f64)
-        self.off = self.D                        # w follows the constants (K) or the population row (K (B + 2))
-        self.D = self.P = self.off + lat.B * lat.n_lat
-        self.m_d, self.s_d = lat.m.to(self.dev).contiguous(), lat.s.to(self.dev).contiguous()
+            s.ode_names, s.ode_mask, s.n_ode, s.sample_nn, s.nn_names = [], 0, 0, True, []
+            s.D = s.P = self.g_K
+            s.mu, s.sd = torch.tensor([0.0], **f64), torch.tensor([1.0], **f64)
+        self.off = s.D                           # w follows the constants (K) or the population row (K (B + 2))
+        s.D = s.P = self.off + lat.B * lat.n_lat
+        self.m_d, self.s_d = lat.m.to(s.dev).contiguous(), lat.s.to(s.dev).contiguous()
 
-    def _start(self):
+    def start(self, s):
         from models.ode_core import ODE_PARAM_NAMES
-        C, B, lat, R = self.C, self.lat.B, self.lat, dict(dtype=self.dt, device=self.dev)
-        if self._pop:
-            z = super()._start()
+        C, B, lat, R = s.C, self.lat.B, self.lat, dict(dtype=s.dt, device=s.dev)
+        if self.inner is not None:
+            z = self.inner.start(s)
         else:
-            self.nn_p = torch.zeros(C, self.P, **R)                  # the coordinate scratch: row stride P = D
-            self.glik = torch.zeros(C, self.P, **R)                  # hode_x0_grad's output, the kernels' gnn
-            self.ode_p = self.ode_base.repeat(C).contiguous()
-            self.nn_rep = self.nn_base.repeat(C).contiguous()
-            z = torch.zeros(C, self.ld, **R)
+            s.nn_p = torch.zeros(C, s.P, **R)                        # the coordinate scratch: row stride P = D
+            s.glik = torch.zeros(C, s.P, **R)                        # hode_x0_grad's output, the kernels' gnn
+            s.ode_p = s.ode_base.repeat(C).contiguous()
+            s.nn_rep = s.nn_base.repeat(C).contiguous()              # the pieces take one copy of the network per chain
+            z = torch.zeros(C, s.ld, **R)
             for i, n in enumerate(self.g_names):
-                z[:, i] = (float(self.ode_base[ODE_PARAM_NAMES.index(n)]) - float(self.g_mu[i])) / float(self.g_sd[i])
-        self.x0_rows = torch.zeros(C * B, 6, **R)                    # hode_x0_params's output: one x0 per (chain, patient)
-        z[:, self.off:self.D] = lat.start().reshape(1, B * lat.n_lat).to(self.dev).to(self.dt)
+                z[:, i] = (float(s.ode_base[ODE_PARAM_NAMES.index(n)]) - float(self.g_mu[i])) / float(self.g_sd[i])
+        s.x0_rows = torch.zeros(C * B, 6, **R)                       # hode_x0_params's output: one x0 per (chain, patient)
+        z[:, self.off:s.D] = lat.start().reshape(1, B * lat.n_lat).to(s.dev).to(s.dt)
         return z
 
-    def initial_jitter(self):
-        """The start + 0.1 N(0, 1) on every coordinate (the chain's own normals)."""
-        self.refresh(_INIT_ITER, 0.0)
-        self.z[:, :self.D].add_(self.p[:, :self.D], alpha=0.1)
+    def initial_jitter(self, s):
+        _jitter_all(s)
 
-    def evaluate(self, n_sets=None):
-        """The likelihood, its gradient in chain coordinates and the solve statuses of all chains, or of the first n_sets rows of
-        the coordinate scratch: (hode_pop_params ->) hode_x0_params -> the pieces (taped solve of one x0 row per trajectory, the
-        per-chain cotangent, the adjoint for gx0 and gode) -> (hode_pop_grad ->) hode_x0_grad."""
-        if not self.has_data:
-            return
-        import models.hybrid_ode_nn as HN
-        A, cap, lat, B = self.C if n_sets is None else int(n_sets), hode.capi, self.lat, self.lat.B
-        x0_args = (A, B, lat.n_lat, self.P, self.off, self.nn_p, lat.lat_mask, lat.link_code, self.m_d, self.s_d)
-        if self._pop:
-            cap.pop_params(A, B, self.K, self.P, self.nn_p, self.pop_mask, self.mu0, self.sd0, self.tau0, self.omega, self.ode_base,
-                           self.ode_p)
-            cap.x0_params(*x0_args, self.x0, self.x0_rows)
-            kw = dict(max_traj=HN.OWN_SETS_MAX, own_sets=True)
+    def evaluate(self, s, A):
+        """(hode_pop_params ->) hode_x0_params -> the pieces (taped solve of one x0 row per trajectory, the per-chain cotangent,
+        the adjoint for gx0 and gode) -> (hode_pop_grad ->) hode_x0_grad."""
+        from models.hybrid_ode_nn import OWN_SETS_MAX
+        cap, lat, B, pop = hode.capi, self.lat, self.lat.B, self.inner
+        x0_args = (A, B, lat.n_lat, s.P, self.off, s.nn_p, lat.lat_mask, lat.link_code, self.m_d, self.s_d)
+        if pop is not None:
+            pop.params(s, A)
+            cap.x0_params(*x0_args, s.x0, s.x0_rows)
+            gx0, _, gode = s._run_pieces(A, (True, False, True), x0=s.x0_rows[:A * B], ode_vec=s.ode_p, nn_flat=s.nn_base,
+                                         max_traj=OWN_SETS_MAX, own_sets=True, own_x0=True)
+            pop.grad(s, A, gode)
+            cap.x0_grad(*x0_args, gx0, s.glik)
         else:
-            cap.x0_params(*x0_args, self.x0, self.x0_rows, self.g_K, self.g_mask, self.g_mu, self.g_sd, self.ode_base, self.ode_p)
-            kw = {}
-        args = self.solve_args
-        self.solve_args = (self.x0_rows[:A * B],) + args[1:]
-        try:
-            gx0, _, gode = self._run_pieces(A, (True, False, self._pop or self.g_K > 0), own_x0=True, **kw)
-        finally:
-            self.solve_args = args
-        if self._pop:
-            cap.pop_grad(A, B, self.K, self.P, self.nn_p, gode, self.pop_mask, self.sd0, self.tau0, self.omega, self.glik)
-            cap.x0_grad(*x0_args, gx0, self.glik)
-            self.gode_sets = gode
-        else:
-            cap.x0_grad(*x0_args, gx0, self.glik, self.g_K, self.g_mask, self.g_sd, gode)
-        self.gx0_rows = gx0
-        self.gnn, self.gode = self.glik, None
-
-
-class _LatentHmc(_LatentState, _Sampler):
-    pass
-
-
-class _LatentNuts(_LatentState, _NutsSampler):
-    pass
-
-
-def _pop_classes():
-    """(HMC, NUTS) samplers of run_population with a latent initial state: this layer in front of the population's."""
-    from inference.population import _Population
-
-    class _PopLatentHmc(_LatentState, _Population, _Sampler):
-        pass
-
-    class _PopLatentNuts(_LatentState, _Population, _NutsSampler):
-        pass
-    return _PopLatentHmc, _PopLatentNuts
+            cap.x0_params(*x0_args, s.x0, s.x0_rows, self.g_K, self.g_mask, self.g_mu, self.g_sd, s.ode_base, s.ode_p)
+            gx0, _, gode = s._run_pieces(A, (True, False, self.g_K > 0), x0=s.x0_rows[:A * B], ode_vec=s.ode_p, nn_flat=s.nn_rep,
+                                         own_x0=True)
+            cap.x0_grad(*x0_args, gx0, s.glik, self.g_K, self.g_mask, self.g_sd, gode)
+            s.gnn, s.gode = s.glik, None
+        s.gx0_rows = gx0
 
 
 # ---------------------------------------------------------------------------------------------------- result
@@ -427,48 +377,3 @@ class LatentStateResult(HMCResult):
         return PR.predictive_summary(self.model, (nn_flat.view(S, -1), ode_vec.view(S, 17)), batch, sigma=sigma, n_bins=n_bins,
                                      max_bytes=PR._DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, solver=solver, rtol=rtol,
                                      atol=atol, quantiles=quantiles, loo=loo, r_eff=r_eff, initial_states=self._kept_x0(thin))
-
-
-# ---------------------------------------------------------------------------------------------------- entry point
-def _run_latent(kind, model, data, initial_state, *, num_samples, num_warmup, n_chains, n_leapfrog=16, max_tree_depth=10, target_accept,
-                noise_sigma, ode_priors, sample_nn, thin, seed, solver, rtol, atol, dtype, jitter, progress, noise, noise_prior,
-                n_patients=None) -> LatentStateResult:
-    """run_hmc (kind "hmc") or run_nuts ("nuts") with initial_state: an InitialStatePrior."""
-    from inference.observation import ObservationModel
-    if sample_nn:
-        raise ValueError("sample_nn=True cannot be combined with initial_state: the network stays at the model's weights "
-                         "(the sampler kernels take no coordinates beyond n_ode + P); pass sample_nn=False")
-    _bind(initial_state, data, n_patients)
-    ObservationModel(noise_sigma, noise, noise_prior)
-    kw = dict(noise_sigma=noise_sigma, ode_priors=ode_priors, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter,
-              noise=noise, noise_prior=noise_prior, initial_state=initial_state, n_patients=n_patients)
-    made, solved = [], []
-    if kind == "hmc":
-        def make():
-            made.append(_LatentHmc(model, data, n_chains, **kw))
-            return made[0]
-
-        def transition(s, it, warm, draws, stats, n_slots, slot):
-            s.refresh(it)
-            s.trajectory(n_leapfrog)
-            s.accept(hode.capi.HMC_ADAPT if warm else hode.capi.HMC_SAMPLE, it, target_accept, draws, stats, n_slots, slot)
-        res = _run_schedule(make, transition, n_stats=4, num_samples=num_samples, num_warmup=num_warmup, thin=thin,
-                            target_accept=target_accept, progress=progress, counts_ok=min(num_samples, n_chains, n_leapfrog, thin) >= 1,
-                            counts_message="num_samples, n_chains, n_leapfrog, thin must be >= 1 and num_warmup >= 0")
-    else:
-        def make():
-            made.append(_LatentNuts(model, data, n_chains, max_tree_depth, **kw))
-            return made[0]
-
-        def transition(s, it, warm, draws, stats, n_slots, slot):
-            s.transition(it)
-            s.finish(warm, target_accept, draws, stats, n_slots, slot)
-            solved.append(s.solved)
-        res = _run_schedule(make, transition, n_stats=6, num_samples=num_samples, num_warmup=num_warmup, thin=thin,
-                            target_accept=target_accept, progress=progress, counts_ok=min(num_samples, n_chains, thin) >= 1,
-                            counts_message="num_samples, n_chains, thin must be >= 1 and num_warmup >= 0",
-                            extra_stats=lambda st: {"tree_depth": st[..., 4].astype(np.int64), "n_leapfrog": st[..., 5].astype(np.int64)},
-                            extra_progress=lambda s: {"leaf_steps": s.leaf_steps})
-        res.stats["trajectories_solved"] = np.asarray(solved, dtype=np.int64)
-    s = made[0]
-    return LatentStateResult(res.draws, s.g_names, s.g_mu.cpu(), s.g_sd.cpu(), s.lat, res.stats, model, s.ode_base, s.nn_base, s.om, data)

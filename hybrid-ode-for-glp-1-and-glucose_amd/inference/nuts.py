@@ -1,7 +1,8 @@
 """Multi-chain No-U-Turn sampling over a HybridODENN on the GPU: `run_nuts`, with the reference's entry point's leading
 arguments (inference/mcmc.py:17: model, data, num_samples, num_warmup, target_accept, max_tree_depth, device).
 
-The density, priors, coordinates, warm-up and result are those of inference.hmc.run_hmc; the transition is multinomial NUTS
+The density, priors, coordinates, warm-up, driver (inference.hmc._run_schedule) and result are those of inference.hmc.run_hmc, and
+so is the target that says what the coordinates mean; the transition is multinomial NUTS
 with the generalised U-turn criterion (Hoffman & Gelman 2014; Betancourt 2017), so the trajectory length adapts per chain
 and per iteration instead of a fixed n_leapfrog.  Every chain builds its tree one leaf per global step: a step is one
 hode_nuts_pre, ONE taped forward solve + adjoint over the A chains whose trees are still growing (their positions ride in the
@@ -10,11 +11,10 @@ A chain whose tree has ended drops out of the solve, so an iteration costs sum_c
 C x max_c leaves_c.  The tree bookkeeping is csrc/hode_nuts.hip; tests/_nuts_reference.py restates it in numpy."""
 from typing import Dict, Optional, Tuple
 
-import numpy as np
 import torch
 
 import hode
-from inference.hmc import HMCResult, _Sampler, _run_schedule
+from inference.hmc import HMCResult, _run, _Sampler
 
 __all__ = ["run_nuts"]
 
@@ -82,25 +82,7 @@ def run_nuts(model, data: Optional[Dict[str, torch.Tensor]], num_samples: int = 
     statistic, and trajectories_solved [iterations] counts the solves of every sampling and warm-up iteration.
 
     initial_state: an `inference.initial_state.InitialStatePrior`, as in run_hmc -> LatentStateResult."""
-    if initial_state is not None:
-        from inference.initial_state import _run_latent
-        return _run_latent("nuts", model, data, initial_state, num_samples=num_samples, num_warmup=num_warmup, n_chains=n_chains,
-                           max_tree_depth=max_tree_depth, target_accept=target_accept, noise_sigma=noise_sigma, ode_priors=ode_priors,
-                           sample_nn=sample_nn, thin=thin, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter,
-                           progress=progress, noise=noise, noise_prior=noise_prior, n_patients=n_patients)
-    solved = []
-
-    def transition(s, it, warm, draws, stats, n_slots, slot):
-        s.transition(it)
-        s.finish(warm, target_accept, draws, stats, n_slots, slot)
-        solved.append(s.solved)
-    res = _run_schedule(lambda: _NutsSampler(model, data, n_chains, max_tree_depth, noise_sigma=noise_sigma, ode_priors=ode_priors,
-                                             sample_nn=sample_nn, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype,
-                                             jitter=jitter, noise=noise, noise_prior=noise_prior),
-                        transition, n_stats=6, num_samples=num_samples, num_warmup=num_warmup, thin=thin, target_accept=target_accept,
-                        progress=progress, counts_ok=min(num_samples, n_chains, thin) >= 1,
-                        counts_message="num_samples, n_chains, thin must be >= 1 and num_warmup >= 0",
-                        extra_stats=lambda st: {"tree_depth": st[..., 4].astype(np.int64), "n_leapfrog": st[..., 5].astype(np.int64)},
-                        extra_progress=lambda s: {"leaf_steps": s.leaf_steps})
-    res.stats["trajectories_solved"] = np.asarray(solved, dtype=np.int64)
-    return res
+    return _run("nuts", model, data, initial_state, n_patients, ode_priors, sample_nn, n_chains=n_chains, max_tree_depth=max_tree_depth,
+                num_samples=num_samples, num_warmup=num_warmup, thin=thin, target_accept=target_accept, progress=progress,
+                noise_sigma=noise_sigma, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter, noise=noise,
+                noise_prior=noise_prior)

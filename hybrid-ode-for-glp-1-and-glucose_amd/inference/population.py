@@ -11,9 +11,10 @@ ascending ODE-index order; `layout`):
     theta_{b,k} = mu_pop_k + tau_k z_{b,k}
     U           = NLL(theta_1..theta_B) + |coords|^2 / 2
 
-The population model is a reparameterisation layer between the samplers' chain coordinates and the solve's per-set constants:
-hode_pop_params maps the coordinates to one row of constants per (chain, patient), hode_pop_grad takes the adjoint's per-set
-gradient back (csrc/hode_population.hip).  The sampler kernels of run_hmc and run_nuts run unchanged: they see the coordinates
+The population model is a reparameterisation layer between the samplers' chain coordinates and the solve's per-set constants,
+the target `_PopulationTarget` that inference.hmc's `_Sampler` / inference.nuts's `_NutsSampler` is handed: hode_pop_params maps
+the coordinates to one row of constants per (chain, patient), hode_pop_grad takes the adjoint's per-set gradient back
+(csrc/hode_population.hip).  The sampler kernels of run_hmc and run_nuts run unchanged: they see the coordinates
 as "P weights with an N(0, 1) prior" (n_ode = 0, sample_nn = True) whose parameter buffer is the coordinate scratch and whose
 likelihood gradient is hode_pop_grad's output.  The solve and the adjoint run with one parameter set per trajectory
 (models.hybrid_ode_nn._run_sets(own_sets=True)); the per-chain likelihood kernels run with set = chain over B T 6 entries."""
@@ -23,8 +24,7 @@ import numpy as np
 import torch
 
 import hode
-from inference.hmc import REFERENCE_PRIORS, HMCResult, _ess, _rank_normal, _rhat, _run_schedule, _Sampler, _split, _INIT_ITER
-from inference.nuts import _NutsSampler
+from inference.hmc import HMCResult, _ess, _jitter_all, _parse_priors, _rank_normal, _rhat, _run_schedule, _split
 
 __all__ = ["run_population", "PopulationResult", "layout"]
 
@@ -39,20 +39,11 @@ def layout(K: int, B: int) -> Dict[str, object]:
 
 def _hyper(ode_priors, tau_scale, tau_log_sd):
     """(names in ascending ODE-index order, mu0, sd0, tau0 as float lists) after the argument checks; no device is touched."""
-    from models.ode_core import ODE_PARAM_NAMES
-    priors = dict(REFERENCE_PRIORS if ode_priors is None else ode_priors)
-    for k in priors:
-        if k not in ODE_PARAM_NAMES:
-            raise ValueError(f"unknown mechanistic constant {k!r}; known: {list(ODE_PARAM_NAMES)}")
-    names = [n for n in ODE_PARAM_NAMES if n in priors]
+    names, _, mu0, sd0 = _parse_priors(ode_priors)
     if not names:
         raise ValueError("nothing to sample: ode_priors names no constant")
     if not float(tau_log_sd) > 0.0:
         raise ValueError("tau_log_sd must be > 0")
-    mu0 = [float(priors[n][0]) for n in names]
-    sd0 = [float(priors[n][1]) for n in names]
-    if min(sd0) <= 0.0:
-        raise ValueError("the prior sd of every constant must be > 0")
     if tau_scale is None:
         tau0 = list(sd0)
     elif isinstance(tau_scale, dict):
@@ -83,13 +74,12 @@ def _init_theta(init, names, B):
     return th
 
 
-class _Population:
-    """Mixin over _Sampler / _NutsSampler: the coordinate layout, the start point and `evaluate` of the population model;
-    everything else (leapfrog, refresh, accept, welford, find_step_size, the NUTS passes) is inherited."""
+class _PopulationTarget:
+    """The population model as a sampler target (inference.hmc._PlainTarget states the protocol): the constructor is the
+    host-side validation; the hyperparameters mu0 / sd0 / tau0 live here, on the device from `layout` on."""
 
-    def __init__(self, model, data, n_chains, *args, n_patients=None, tau_scale=None, tau_log_sd=0.5, init=None, ode_priors=None,
-                 **kw):
-        self.pop_names, mu0, sd0, tau0 = _hyper(ode_priors, tau_scale, tau_log_sd)
+    def __init__(self, data, n_patients=None, ode_priors=None, tau_scale=None, tau_log_sd=0.5, init=None):
+        self.pop_names, *self._hyp = _hyper(ode_priors, tau_scale, tau_log_sd)
         if data is None:
             if n_patients is None or int(n_patients) < 1:
                 raise ValueError("data=None samples the prior: give n_patients >= 1")
@@ -99,64 +89,53 @@ class _Population:
             if n_patients is not None and int(n_patients) != self.B:
                 raise ValueError(f"n_patients = {n_patients} but the batch holds {self.B}")
         self.K, self.omega = len(self.pop_names), float(tau_log_sd)
-        self._hyp = (mu0, sd0, tau0)
         self._init = _init_theta(init, self.pop_names, self.B)
-        kw.pop("sample_nn", None)
-        super().__init__(model, data, n_chains, *args, ode_priors=ode_priors, sample_nn=True, **kw)
-        if self.has_data:       # the solve takes the per-(chain, patient) constants and ONE network (_run_sets(own_sets=True))
-            self.solve_args = self.solve_args[:5] + (self.ode_p, self.nn_base) + self.solve_args[7:]
 
-    def _layout(self, ode_priors, sample_nn):
+    def layout(self, s):
         from models.ode_core import ODE_PARAM_NAMES
-        f64 = dict(dtype=torch.float64, device=self.dev)
+        f64 = dict(dtype=torch.float64, device=s.dev)
         self.pop_mask = sum(1 << ODE_PARAM_NAMES.index(n) for n in self.pop_names)
         self.mu0, self.sd0, self.tau0 = (torch.tensor(v, **f64) for v in self._hyp)
         # what the sampler kernels see: no constants of their own, D = P "weights" whose buffer is the coordinate scratch
-        self.ode_names, self.ode_mask, self.n_ode, self.sample_nn, self.nn_names = [], 0, 0, True, []
-        self.D = self.P = layout(self.K, self.B)["D"]
-        self.mu, self.sd = torch.tensor([0.0], **f64), torch.tensor([1.0], **f64)
+        s.ode_names, s.ode_mask, s.n_ode, s.sample_nn, s.nn_names = [], 0, 0, True, []
+        s.D = s.P = layout(self.K, self.B)["D"]
+        s.mu, s.sd = torch.tensor([0.0], **f64), torch.tensor([1.0], **f64)
 
-    def _start(self):
+    def start(self, s):
         from models.ode_core import ODE_PARAM_NAMES
-        C, K, B, R = self.C, self.K, self.B, dict(dtype=self.dt, device=self.dev)
-        self.nn_p = torch.zeros(C, self.P, **R)                    # the coordinate scratch: row stride P = D
-        self.glik = torch.zeros(C, self.P, **R)                    # hode_pop_grad's output, the kernels' gnn
-        self.ode_p = torch.empty(C * B * 17, **R)
+        C, K, B, R = s.C, self.K, self.B, dict(dtype=s.dt, device=s.dev)
+        s.nn_p = torch.zeros(C, s.P, **R)                          # the coordinate scratch: row stride P = D
+        s.glik = torch.zeros(C, s.P, **R)                          # hode_pop_grad's output, the kernels' gnn
+        s.ode_p = torch.empty(C * B * 17, **R)
         lay = layout(K, B)
-        base = torch.stack([self.ode_base[ODE_PARAM_NAMES.index(n)] for n in self.pop_names]).double()
-        z = torch.zeros(C, self.ld, **R)
-        z[:, lay["m"]] = ((base - self.mu0) / self.sd0).to(self.dt)
+        base = torch.stack([s.ode_base[ODE_PARAM_NAMES.index(n)] for n in self.pop_names]).double()
+        z = torch.zeros(C, s.ld, **R)
+        z[:, lay["m"]] = ((base - self.mu0) / self.sd0).to(s.dt)
         if self._init is not None:
-            zb = ((self._init.to(self.dev) - base) / self.tau0).clamp(-3.0, 3.0)
-            z[:, lay["z"]] = zb.reshape(1, B * K).to(self.dt)
+            zb = ((self._init.to(s.dev) - base) / self.tau0).clamp(-3.0, 3.0)
+            z[:, lay["z"]] = zb.reshape(1, B * K).to(s.dt)
         return z
 
-    def initial_jitter(self):
-        """The start + 0.1 N(0, 1) on every coordinate (the chain's own normals)."""
-        self.refresh(_INIT_ITER, 0.0)
-        self.z[:, :self.D].add_(self.p[:, :self.D], alpha=0.1)
+    def initial_jitter(self, s):
+        _jitter_all(s)
 
-    def evaluate(self, n_sets=None):
-        """The likelihood, its gradient in chain coordinates and the solve statuses of all chains, or of the first n_sets rows of
-        the coordinate scratch: hode_pop_params -> the pieces (taped solve, the per-chain cotangent, the adjoint for gode) ->
-        hode_pop_grad."""
-        if not self.has_data:
-            return
-        import models.hybrid_ode_nn as HN
-        A, cap = self.C if n_sets is None else int(n_sets), hode.capi
-        cap.pop_params(A, self.B, self.K, self.P, self.nn_p, self.pop_mask, self.mu0, self.sd0, self.tau0, self.omega, self.ode_base,
-                       self.ode_p)
-        _, _, gode = self._run_pieces(A, (False, False, True), max_traj=HN.OWN_SETS_MAX, own_sets=True)
-        cap.pop_grad(A, self.B, self.K, self.P, self.nn_p, gode, self.pop_mask, self.sd0, self.tau0, self.omega, self.glik)
-        self.gnn, self.gode, self.gode_sets = self.glik, None, gode
+    def params(self, s, A):
+        """hode_pop_params: the first A rows of the coordinate scratch -> one row of constants per (chain, patient) in ode_p."""
+        hode.capi.pop_params(A, self.B, self.K, s.P, s.nn_p, self.pop_mask, self.mu0, self.sd0, self.tau0, self.omega, s.ode_base, s.ode_p)
 
+    def grad(self, s, A, gode):
+        """hode_pop_grad: the adjoint's per-set gode -> glik, the kernels' gnn."""
+        hode.capi.pop_grad(A, self.B, self.K, s.P, s.nn_p, gode, self.pop_mask, self.sd0, self.tau0, self.omega, s.glik)
+        s.gnn, s.gode, s.gode_sets = s.glik, None, gode
 
-class _PopulationHmc(_Population, _Sampler):
-    pass
-
-
-class _PopulationNuts(_Population, _NutsSampler):
-    pass
+    def evaluate(self, s, A):
+        """hode_pop_params -> the pieces (taped solve of the per-(chain, patient) constants and ONE network, the per-chain
+        cotangent, the adjoint for gode) -> hode_pop_grad."""
+        from models.hybrid_ode_nn import OWN_SETS_MAX
+        self.params(s, A)
+        _, _, gode = s._run_pieces(A, (False, False, True), x0=s.x0, ode_vec=s.ode_p, nn_flat=s.nn_base, max_traj=OWN_SETS_MAX,
+                                   own_sets=True)
+        self.grad(s, A, gode)
 
 
 # ---------------------------------------------------------------------------------------------------- result
@@ -394,52 +373,15 @@ def run_population(model, data: Optional[Dict[str, torch.Tensor]], num_samples: 
     (inference/initial_state.py) makes the chosen components of every patient's initial state latent; the row is then
     [ m | s | z | w ] with w from column K (B + 2), and the result's `initial_states()`, `predict` and `predictive_summary` pair
     every draw with its own x0."""
-    from inference.observation import ObservationModel
     if sampler not in ("hmc", "nuts"):
         raise ValueError(f"sampler must be 'hmc' or 'nuts', not {sampler!r}")
-    names, *_ = _hyper(ode_priors, tau_scale, tau_log_sd)
-    if data is None and (n_patients is None or int(n_patients) < 1):
-        raise ValueError("data=None samples the prior: give n_patients >= 1")
-    B = int(n_patients) if data is None else int(data["initial_state"].shape[0])
-    _init_theta(init, names, B)
-    ObservationModel(noise_sigma, noise, noise_prior)
-    hmc_cls, nuts_cls = _PopulationHmc, _PopulationNuts
+    t = pop = _PopulationTarget(data, n_patients, ode_priors, tau_scale, tau_log_sd, init)
     if initial_state is not None:
-        from inference import initial_state as IS
-        IS._bind(initial_state, data, n_patients)
-        hmc_cls, nuts_cls = IS._pop_classes()
-    kw = dict(noise_sigma=noise_sigma, ode_priors=ode_priors, seed=seed, solver=solver, rtol=rtol, atol=atol, dtype=dtype, jitter=jitter,
-              noise=noise, noise_prior=noise_prior, n_patients=n_patients, tau_scale=tau_scale, tau_log_sd=tau_log_sd, init=init)
-    if initial_state is not None:
-        kw["initial_state"] = initial_state
-    made, solved = [], []
-    if sampler == "hmc":
-        def make():
-            made.append(hmc_cls(model, data, n_chains, **kw))
-            return made[0]
-
-        def transition(s, it, warm, draws, stats, n_slots, slot):
-            s.refresh(it)
-            s.trajectory(n_leapfrog)
-            s.accept(hode.capi.HMC_ADAPT if warm else hode.capi.HMC_SAMPLE, it, target_accept, draws, stats, n_slots, slot)
-        res = _run_schedule(make, transition, n_stats=4, num_samples=num_samples, num_warmup=num_warmup, thin=thin,
-                            target_accept=target_accept, progress=progress, counts_ok=min(num_samples, n_chains, n_leapfrog, thin) >= 1,
-                            counts_message="num_samples, n_chains, n_leapfrog, thin must be >= 1 and num_warmup >= 0")
-    else:
-        def make():
-            made.append(nuts_cls(model, data, n_chains, max_tree_depth, **kw))
-            return made[0]
-
-        def transition(s, it, warm, draws, stats, n_slots, slot):
-            s.transition(it)
-            s.finish(warm, target_accept, draws, stats, n_slots, slot)
-            solved.append(s.solved)
-        res = _run_schedule(make, transition, n_stats=6, num_samples=num_samples, num_warmup=num_warmup, thin=thin,
-                            target_accept=target_accept, progress=progress, counts_ok=min(num_samples, n_chains, thin) >= 1,
-                            counts_message="num_samples, n_chains, thin must be >= 1 and num_warmup >= 0",
-                            extra_stats=lambda st: {"tree_depth": st[..., 4].astype(np.int64), "n_leapfrog": st[..., 5].astype(np.int64)},
-                            extra_progress=lambda s: {"leaf_steps": s.leaf_steps})
-        res.stats["trajectories_solved"] = np.asarray(solved, dtype=np.int64)
-    s = made[0]
-    return PopulationResult(res.draws, s.pop_names, s.B, s.mu0.cpu(), s.sd0.cpu(), s.tau0.cpu(), s.omega, res.stats, model, s.ode_base,
-                            s.nn_base, s.om, data, getattr(s, "lat", None))
+        from inference.initial_state import _LatentTarget
+        t = _LatentTarget(initial_state, data, n_patients, inner=pop)          # the latent states stand in front of the population
+    s, draws, stats = _run_schedule(sampler, model, data, target=t, n_chains=n_chains, n_leapfrog=n_leapfrog, max_tree_depth=max_tree_depth,
+                                    num_samples=num_samples, num_warmup=num_warmup, thin=thin, target_accept=target_accept,
+                                    progress=progress, noise_sigma=noise_sigma, seed=seed, solver=solver, rtol=rtol, atol=atol,
+                                    dtype=dtype, jitter=jitter, noise=noise, noise_prior=noise_prior)
+    return PopulationResult(draws, pop.pop_names, pop.B, pop.mu0.cpu(), pop.sd0.cpu(), pop.tau0.cpu(), pop.omega, stats, model, s.ode_base,
+                            s.nn_base, s.om, data, None if t is pop else t.lat)

@@ -261,9 +261,11 @@ def test_own_x0_through_run_sets_vs_oracle(dt, own_sets):
 
 
 def _latent_sampler(m, data, C, pop=False, **kw):
-    from inference.initial_state import _LatentHmc, _pop_classes
-    cls = _pop_classes()[0] if pop else _LatentHmc
-    return cls(m, data, C, **kw)
+    from inference.hmc import _Sampler
+    from inference.initial_state import _LatentTarget
+    from inference.population import _PopulationTarget
+    t = _LatentTarget(kw.pop("initial_state"), data, ode_priors=kw.pop("ode_priors", None), inner=_PopulationTarget(data) if pop else None)
+    return _Sampler(m, data, C, target=t, **kw)
 
 
 @pytest.mark.parametrize("own_sets", [False, True])
@@ -301,7 +303,7 @@ def test_chains_cut_into_patient_slices_reproduce_the_uncut_run(monkeypatch, dt,
     print(f"\ncut chains {dt} own_sets={own_sets}: loss_sum rel {rel:.2e}")
     assert rel <= 1e-15
     assert torch.equal(s.gx0_rows, gx0) and torch.equal(Y, y) and torch.equal(s.status, status)
-    assert torch.equal(s.glik[:, s.off:], glik[:, s.off:])               # (a chain's gode is summed over its slices: not bitwise)
+    assert torch.equal(s.glik[:, s.target.off:], glik[:, s.target.off:])               # (a chain's gode is summed over its slices: not bitwise)
     if own_sets:
         assert torch.equal(s.glik, glik)                                 # one gode row per trajectory: nothing is summed across slices
 
@@ -322,27 +324,28 @@ def _small_sampler(kind, link, C=3):
 def _torch_U_grad(s, z):
     """U and grad U by ONE fp64 solve of the mapped rows, the residuals, the adjoint, and the map and its transpose in torch."""
     from models.ode_core import ODE_PARAM_NAMES
-    C, B, lat, off = s.C, s.lat.B, s.lat, s.off
+    t, pop = s.target, s.target.inner
+    C, B, lat, off = s.C, t.lat.B, t.lat, t.off
     zd = z[:, :s.D].double()
     w = zd[:, off:].reshape(C, B, lat.n_lat)
     ml, sl = lat.m[:, lat.states].to(DEV), lat.s[:, lat.states].to(DEV)
     xl = ml * torch.exp(sl * w) if lat.link_code else ml + sl * w
     x0 = s.x0.double().unsqueeze(0).repeat(C, 1, 1)
     x0[..., lat.states] = xl
-    if s._pop:
-        K, om = s.K, s.omega
+    if pop is not None:
+        K, om = pop.K, pop.omega
         m_, s_, zz = zd[:, :K], zd[:, K:2 * K], zd[:, 2 * K:off].reshape(C, B, K)
-        mu, tau = s.mu0 + s.sd0 * m_, s.tau0 * torch.exp(om * s_)
-        idx = [ODE_PARAM_NAMES.index(n) for n in s.pop_names]
+        mu, tau = pop.mu0 + pop.sd0 * m_, pop.tau0 * torch.exp(om * s_)
+        idx = [ODE_PARAM_NAMES.index(n) for n in pop.pop_names]
         ode = s.ode_base.double().reshape(1, 17).repeat(C * B, 1)
         ode[:, idx] = (mu.unsqueeze(1) + tau.unsqueeze(1) * zz).reshape(C * B, K)
         n_sets = C * B
     else:
-        K = s.g_K
-        idx = [ODE_PARAM_NAMES.index(n) for n in s.g_names]
+        K = t.g_K
+        idx = [ODE_PARAM_NAMES.index(n) for n in t.g_names]
         ode = s.ode_base.double().reshape(1, 17).repeat(C, 1)
         if K:
-            ode[:, idx] = s.g_mu + s.g_sd * zd[:, :K]
+            ode[:, idx] = t.g_mu + t.g_sd * zd[:, :K]
         n_sets = C
     sol = hode.solve_fwd(x0.reshape(C * B, 6).contiguous(), s.t, None, None, None, ode.reshape(-1), s.nn_base.double().repeat(n_sets), s.H, s.L,
                          method=hode.METHOD_RK4, n_sets=n_sets, want_tape=True)
@@ -350,11 +353,11 @@ def _torch_U_grad(s, z):
     ss = (r ** 2).sum((1, 2))
     gx0, _, gode = hode.solve_bwd(sol, (2 * s.lik_scale * r).view_as(sol.y), want_gnn=False, want_gode=K > 0)
     gw = (gx0.view(C, B, 6)[..., lat.states] * (sl * xl if lat.link_code else sl)).reshape(C, -1)
-    if s._pop:
+    if pop is not None:
         G = gode.view(C, B, 17)[:, :, idx]
-        parts = [s.sd0 * G.sum(1), om * tau * (G * zz).sum(1), (tau.unsqueeze(1) * G).reshape(C, B * K), gw]
+        parts = [pop.sd0 * G.sum(1), om * tau * (G * zz).sum(1), (tau.unsqueeze(1) * G).reshape(C, B * K), gw]
     else:
-        parts = ([s.g_sd * gode.view(C, 17)[:, idx]] if K else []) + [gw]
+        parts = ([t.g_sd * gode.view(C, 17)[:, idx]] if K else []) + [gw]
     return s.lik_scale * ss + 0.5 * (zd ** 2).sum(1), torch.cat(parts, 1) + zd
 
 
@@ -366,7 +369,7 @@ def test_one_trajectory_matches_torch_fp64_and_is_reversible(kind, link):
     1e-12, reversed to 1e-10."""
     s = _small_sampler(kind, link)
     n_w = 3 * 3
-    assert (s.off, s.D) == {"K7": (7, 7 + n_w), "K0": (0, n_w), "pop": (35, 35 + n_w)}[kind] and s.ld == (s.D + 3) // 4 * 4
+    assert (s.target.off, s.D) == {"K7": (7, 7 + n_w), "K0": (0, n_w), "pop": (35, 35 + n_w)}[kind] and s.ld == (s.D + 3) // 4 * 4
     s.log_eps.fill_(math.log(0.02))
     s.refresh(5)
     z0, p0 = s.z.clone(), s.p.clone()

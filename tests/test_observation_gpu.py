@@ -203,12 +203,12 @@ def _masked(data, seed=4, garbage=float("nan")):
     return dict(data, observations=obs, observation_mask=mask)
 
 
-def _obs_sampler(C=3, marginal=False, dtype=torch.float64, solver="rk4", garbage=float("nan"), B=2, T=5, cls=None, **kw):
+def _obs_sampler(C=3, marginal=False, dtype=torch.float64, solver="rk4", garbage=float("nan"), B=2, T=5, **kw):
     from inference.hmc import _Sampler
     m = _model(16, 2)
     data = _masked(_data(m, B=B, T=T, sigma=0.2), garbage=garbage)
-    s = (cls or _Sampler)(m, data, C, noise_sigma=SIG6, noise="marginal" if marginal else "fixed", seed=11, solver=solver, dtype=dtype,
-                          jitter=0.0, **kw)
+    s = _Sampler(m, data, C, noise_sigma=SIG6, noise="marginal" if marginal else "fixed", seed=11, solver=solver, dtype=dtype,
+                 jitter=0.0, **kw)             # (kw may hold target=: another posterior over the same observation model)
     s.initial_jitter()
     s.gradient()
     return s, data

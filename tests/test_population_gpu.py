@@ -156,10 +156,11 @@ def test_pop_grad_is_the_transpose_of_pop_params(A, B, K):
 
 # ------------------------------------------------------------------ 3. U and grad U end to end
 def _small_sampler(C=3, **kw):
-    from inference.population import _PopulationHmc
+    from inference.hmc import _Sampler
+    from inference.population import _PopulationTarget
     m = _model(16, 2)
     data = _data(m, B=3, T=5, sigma=0.2, ode={"a_GI": [0.0095, 0.0104, 0.0115]})
-    s = _PopulationHmc(m, data, C, noise_sigma=0.2, seed=11, solver="rk4", dtype=torch.float64, jitter=0.0, **kw)
+    s = _Sampler(m, data, C, noise_sigma=0.2, seed=11, solver="rk4", dtype=torch.float64, jitter=0.0, target=_PopulationTarget(data, **kw))
     s.initial_jitter()
     s.gradient()
     return s
@@ -168,12 +169,13 @@ def _small_sampler(C=3, **kw):
 def _torch_U_grad(s, z):
     """U and grad U by ONE fp64 solve with n_sets = C B, the residuals, the adjoint, and the map and its transpose in torch."""
     from models.ode_core import ODE_PARAM_NAMES
-    C, B, K, w = s.C, s.B, s.K, s.omega
+    t = s.target
+    C, B, K, w = s.C, t.B, t.K, t.omega
     zd = z[:, :s.D].double()
     m_, s_, zz = zd[:, :K], zd[:, K:2 * K], zd[:, 2 * K:].reshape(C, B, K)
-    mu, tau = s.mu0 + s.sd0 * m_, s.tau0 * torch.exp(w * s_)
+    mu, tau = t.mu0 + t.sd0 * m_, t.tau0 * torch.exp(w * s_)
     theta = mu.unsqueeze(1) + tau.unsqueeze(1) * zz
-    idx = [ODE_PARAM_NAMES.index(n) for n in s.pop_names]
+    idx = [ODE_PARAM_NAMES.index(n) for n in t.pop_names]
     ode = s.ode_base.double().reshape(1, 17).repeat(C * B, 1)
     ode[:, idx] = theta.reshape(C * B, K)
     sol = hode.solve_fwd(s.x0.repeat(C, 1), s.t, None, None, None, ode.reshape(-1), s.nn_base.double().repeat(C * B), s.H, s.L,
@@ -182,13 +184,13 @@ def _torch_U_grad(s, z):
     ss = (r ** 2).sum((1, 2))
     _, _, gode = hode.solve_bwd(sol, (2 * s.lik_scale * r).view_as(sol.y), want_gnn=False, want_gode=True)
     G = gode.view(C, B, 17)[:, :, idx]
-    grad = torch.cat([s.sd0 * G.sum(1), w * tau * (G * zz).sum(1), (tau.unsqueeze(1) * G).reshape(C, B * K)], 1) + zd
+    grad = torch.cat([t.sd0 * G.sum(1), w * tau * (G * zz).sum(1), (tau.unsqueeze(1) * G).reshape(C, B * K)], 1) + zd
     return s.lik_scale * ss + 0.5 * (zd ** 2).sum(1), grad
 
 
 def test_one_trajectory_matches_torch_fp64_and_is_reversible():
     s = _small_sampler()
-    assert s.D == 7 * 5 and s.ld == 36 and s.K == 7
+    assert s.D == 7 * 5 and s.ld == 36 and s.target.K == 7
     s.log_eps.fill_(math.log(0.02))
     s.refresh(5)
     z0, p0 = s.z.clone(), s.p.clone()
@@ -291,10 +293,11 @@ def test_a_chain_cut_into_patient_slices_reproduces_the_uncut_run(monkeypatch, d
     """A tape budget of 24 trajectories cuts every chain's 64 patients into three slices: loss_sum to 1e-15 relative, gode
     bitwise."""
     import models.hybrid_ode_nn as HN
-    from inference.population import _PopulationHmc
+    from inference.hmc import _Sampler
+    from inference.population import _PopulationTarget
     m = _model()
     data = _data(m, B=64, T=5, sigma=0.2)
-    s = _PopulationHmc(m, data, 5, noise_sigma=0.2, seed=3, dtype=dt)
+    s = _Sampler(m, data, 5, noise_sigma=0.2, seed=3, dtype=dt, target=_PopulationTarget(data))
     s.initial_jitter()
     s.leapfrog(hode.capi.HMC_PARAMS)
     s.evaluate()
@@ -318,10 +321,11 @@ def test_trajectories_out_of_tape_steps_are_retried_in_one_launch(monkeypatch):
     with their own constants in ONE launch, whatever their number, and loss_sum and gode are those of the run whose tape held
     every step.  fp64, the same discrete scheme and step sequence either way: 1e-12 / 1e-9 relative (summation order only)."""
     import models.hybrid_ode_nn as HN
-    from inference.population import _PopulationHmc
+    from inference.hmc import _Sampler
+    from inference.population import _PopulationTarget
     m = _model()
     data = _data(m, B=8, T=13, sigma=0.2)
-    s = _PopulationHmc(m, data, 3, noise_sigma=0.2, seed=3, dtype=torch.float64)
+    s = _Sampler(m, data, 3, noise_sigma=0.2, seed=3, dtype=torch.float64, target=_PopulationTarget(data))
     s.initial_jitter()
     s.leapfrog(hode.capi.HMC_PARAMS)
     seen, real = [], HN._solve_taped
@@ -498,14 +502,15 @@ def test_failed_solves_are_rejected_and_counted():
 
 def test_init_from_fit_patients_starts_at_a_lower_U():
     from inference import fit_patients
-    from inference.population import _PopulationHmc
+    from inference.hmc import _Sampler
+    from inference.population import _PopulationTarget
     m = _model()
     pri = {"a_GI": (0.0104, 0.002), "k_I": (0.025, 0.005)}
     data = _data(m, B=4, T=13, sigma=0.05, ode={"a_GI": [0.0085, 0.0100, 0.0110, 0.0125], "k_I": [0.021, 0.024, 0.027, 0.030]})
     fit = fit_patients(m, data, params=("a_GI", "k_I"), noise_sigma=0.05, priors=pri)
     U = []
     for init in (None, fit, torch.stack([fit.params["a_GI"], fit.params["k_I"]], 1)):
-        s = _PopulationHmc(m, data, 2, noise_sigma=0.05, ode_priors=pri, init=init)
+        s = _Sampler(m, data, 2, noise_sigma=0.05, target=_PopulationTarget(data, ode_priors=pri, init=init))
         s.gradient()
         U.append(s.U.clone())
     print(f"\nU at the default start {U[0].tolist()}, from the fit {U[1].tolist()}")

@@ -53,13 +53,13 @@ def bench(C, L, repeats, data):
     import hode
     from inference import InitialStatePrior
     from inference.hmc import _Sampler
-    from inference.initial_state import _LatentHmc
+    from inference.initial_state import _LatentTarget
     from models.hybrid_ode_nn import HybridODENN
     torch.manual_seed(0)
     m = HybridODENN(nn_hidden=H, nn_layers=L_NN, device="cuda")
     prior = InitialStatePrior.from_batch(data, states=("G", "I", "Glu", "GLP1"), inflate=1.0)
     plain = _Sampler(m, data, C, sample_nn=False, seed=0)
-    latent = _LatentHmc(m, data, C, seed=0, initial_state=prior)
+    latent = _Sampler(m, data, C, seed=0, target=_LatentTarget(prior, data))
     its = []
     for s in (plain, latent):
         s.initial_jitter()
@@ -75,18 +75,19 @@ def bench(C, L, repeats, data):
         its.append(iteration)
     (t_plain, t_latent), (r_plain, r_latent) = _alternate(its, 1, repeats)
     (e_plain, e_latent), _ = _alternate([plain.evaluate, latent.evaluate], 1, repeats)
-    lat, cap = latent.lat, hode.capi
-    args = (C, lat.B, lat.n_lat, latent.P, latent.off, latent.nn_p, lat.lat_mask, lat.link_code, latent.m_d, latent.s_d)
+    tg, cap = latent.target, hode.capi
+    lat = tg.lat
+    args = (C, lat.B, lat.n_lat, latent.P, tg.off, latent.nn_p, lat.lat_mask, lat.link_code, tg.m_d, tg.s_d)
     gx0 = torch.randn(C * lat.B, 6, dtype=latent.dt, device=latent.dev)
     gode = torch.randn(C, 17, dtype=latent.dt, device=latent.dev)
 
     def k_params():
-        cap.x0_params(*args, latent.x0, latent.x0_rows, latent.g_K, latent.g_mask, latent.g_mu, latent.g_sd, latent.ode_base, latent.ode_p)
+        cap.x0_params(*args, latent.x0, latent.x0_rows, tg.g_K, tg.g_mask, tg.g_mu, tg.g_sd, latent.ode_base, latent.ode_p)
 
     def k_grad():
-        cap.x0_grad(*args, gx0, latent.glik, latent.g_K, latent.g_mask, latent.g_sd, gode)
+        cap.x0_grad(*args, gx0, latent.glik, tg.g_K, tg.g_mask, tg.g_sd, gode)
     (k_p, k_g), _ = _alternate([k_params, k_grad], 200, repeats)
-    return {"chains": C, "patients": B, "points": T, "K": latent.g_K, "n_lat": lat.n_lat, "D_plain": plain.D, "D_latent": latent.D,
+    return {"chains": C, "patients": B, "points": T, "K": tg.g_K, "n_lat": lat.n_lat, "D_plain": plain.D, "D_latent": latent.D,
             "trajectories": C * B, "leapfrog": L, "repeats": repeats,
             "hmc_iteration_s": {"plain": t_plain, "latent": t_latent, "ratio": t_latent / t_plain,
                                 "plain_min_max": r_plain, "latent_min_max": r_latent},

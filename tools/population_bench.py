@@ -42,11 +42,11 @@ def _time(fn, iters):
 def bench(C, iters, L, data):
     import torch
     from inference.hmc import _Sampler
-    from inference.population import _PopulationHmc
+    from inference.population import _PopulationTarget
     from models.hybrid_ode_nn import HybridODENN
     torch.manual_seed(0)
     m = HybridODENN(nn_hidden=H, nn_layers=L_NN, device="cuda")
-    s = _PopulationHmc(m, data, C, seed=0)
+    s = _Sampler(m, data, C, seed=0, target=_PopulationTarget(data))
     s.initial_jitter()
     s.gradient()
     s.log_eps.fill_(-7.0)                  # a small step: every proposal stays where the solve is well behaved
@@ -63,7 +63,7 @@ def bench(C, iters, L, data):
     h.initial_jitter()
     h.gradient()
     t_hmc = _time(h.evaluate, iters)
-    return {"chains": C, "patients": B, "points": T, "K": s.K, "D": s.D, "trajectories": C * B, "leapfrog": L,
+    return {"chains": C, "patients": B, "points": T, "K": s.target.K, "D": s.D, "trajectories": C * B, "leapfrog": L,
             "evaluate_s": t_eval, "hmc_iteration_s": t_iter, "run_hmc_evaluate_s": t_hmc, "evaluate_ratio": t_eval / t_hmc,
             "network_copies_bytes": min(C * B, 1024) * s.nn_base.numel() * s.nn_base.element_size()}
 
