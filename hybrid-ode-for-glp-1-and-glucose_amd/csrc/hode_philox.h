@@ -27,6 +27,9 @@ constexpr uint32_t kRngSobol = 7;
 // group 2 i + (j >> 2) gives particle i the normals of its states 4 (j >> 2) .. 4 (j >> 2) + 3; resampling: group 0, one
 // uniform per patient and step
 constexpr uint32_t kRngFilterNoise = 8, kRngFilterResample = 9;
+// backward simulation over a stored filter (hode_smooth.hip): the step whose slot is drawn as the iteration, the trajectory m
+// as the group, one uniform per draw
+constexpr uint32_t kRngFilterSmooth = 10;
 
 struct Philox4 { uint32_t x, y, z, w; };
 

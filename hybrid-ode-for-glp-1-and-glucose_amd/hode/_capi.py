@@ -34,7 +34,7 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_pred_loo_fold_f32", "hode_pred_loo_fold_f64", "hode_pred_loo_finish_f32", "hode_pred_loo_finish_f64",
            "hode_pop_params_f32", "hode_pop_params_f64", "hode_pop_grad_f32", "hode_pop_grad_f64",
            "hode_x0_params_f32", "hode_x0_params_f64", "hode_x0_grad_f32", "hode_x0_grad_f64",
-           "hode_pf_step_f32", "hode_pf_step_f64"]
+           "hode_pf_step_f32", "hode_pf_step_f64", "hode_pf_smooth_f32", "hode_pf_smooth_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -496,6 +496,39 @@ def pf_step(x_in, obs, sigma, q, dt, lw, step, seed=0, id0=0, link=1, ess_frac=0
         C.c_int(int(link)), C.c_double(float(ess_frac)), _ptr(lw), _ptr(x_out), _ptr(anc), _ptr(stats), C.c_int(n_aux), _ptr(aux_in),
         _ptr(aux_out)), "hode_pf_step")
     return x_out, anc, stats, aux_out
+
+
+def pf_smooth(hist, lwh, pred, q, dt, M, seed=0, id0=0, link=1, out=None):
+    """Backward-simulation smoothing over a stored filter (include/hode.h "Particle smoother"): hist / pred [S, B, N, 6] fp32 or
+    fp64 on the device (the particles after each step, and the state each was carried to before the noise), lwh fp64 [S, B, N],
+    q fp64 [6], dt fp64 [S, B]; M trajectories per patient.  `out`: (idx, paths) buffers to write into, else they are allocated.
+    Returns (idx int32 [S, B, M], paths [S, B, M, 6])."""
+    _need_gpu(hist)
+    if hist.dim() != 4 or hist.shape[3] != 6 or not hist.is_contiguous():
+        raise HodeError("pf_smooth: hist must be a contiguous [S, B, N, 6]")
+    S, B, N = (int(v) for v in hist.shape[:3])
+    dev, dt_ = hist.device, hist.dtype
+    M = int(M)
+    if M < 1:
+        raise HodeError("pf_smooth: M must be at least 1")
+    if N > PF_MAX_PARTICLES:
+        raise HodeError(f"pf_smooth: N = {N} particles, the kernel takes up to {PF_MAX_PARTICLES} (HODE_PF_MAX_PARTICLES)")
+    if pred.shape != hist.shape or pred.dtype != dt_ or pred.device != dev or not pred.is_contiguous():
+        raise HodeError("pf_smooth: pred must be a contiguous [S, B, N, 6] of hist's dtype")
+    for name, v, n in (("lwh", lwh, S * B * N), ("q", q, 6), ("dt", dt, S * B)):
+        if v.dtype != torch.float64 or v.device != dev or v.numel() != n or not v.is_contiguous():
+            raise HodeError(f"pf_smooth: {name} must be a contiguous fp64 device tensor of {n} elements")
+    if out is None:
+        out = (torch.empty(S, B, M, dtype=torch.int32, device=dev), torch.empty(S, B, M, 6, dtype=dt_, device=dev))
+    idx, paths = out
+    if (idx.dtype != torch.int32 or tuple(idx.shape) != (S, B, M) or idx.device != dev or not idx.is_contiguous()
+            or paths.dtype != dt_ or tuple(paths.shape) != (S, B, M, 6) or paths.device != dev or not paths.is_contiguous()):
+        raise HodeError("pf_smooth: out must be (idx int32 [S, B, M], paths [S, B, M, 6] of hist's dtype), contiguous")
+    _check(getattr(load(), f"hode_pf_smooth_{_sfx(dt_)}")(
+        _stream(), C.c_int(B), C.c_int(N), C.c_int(M), C.c_int(S), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+        C.c_uint32(int(id0) & 0xFFFFFFFF), _ptr(hist), _ptr(lwh), _ptr(pred), _ptr(q), _ptr(dt), C.c_int(int(link)), _ptr(idx),
+        _ptr(paths)), "hode_pf_smooth")
+    return idx, paths
 
 
 PRED_MAX_BINS, PRED_FIXED_COLS, PRED_SCORE_BLOCKS = 32, 16, 128

@@ -6,7 +6,9 @@ of a model with process noise (csrc/hode_filter.hip; include/hode.h, "Particle f
                     in its own row) and ONE launch of the step kernel: process noise, weights under the observation model,
                     normalisation, ESS, systematic resampling, the gather.  Nothing is read back to the host inside the loop.
     FilterResult    the filtered moments, ESS, log-evidence increments, the final particles; `forecast` continues the same loop
-                    without observations; with store_particles=True the history, the ancestors and `smoothed()`.
+                    without observations; with store_particles=True the history, the ancestors, `smoothed()` (genealogy
+                    tracing) and `smooth()`: backward-simulation smoothing, ONE launch of csrc/hode_smooth.hip over the stored
+                    steps (include/hode.h, "Particle smoother") -> SmoothResult.
 
 The state model: between two filter steps a particle follows the deterministic solve; at a step it is disturbed by noise of
 standard deviation process_noise * sqrt(time since the previous step) -- additive, or on the logarithm (the default: states stay
@@ -22,7 +24,7 @@ from models.ode_core import ODE_PARAM_NAMES
 
 from .observation import ObservationModel
 
-__all__ = ["FilterResult", "run_filter"]
+__all__ = ["FilterResult", "SmoothResult", "run_filter"]
 
 MAX_PARTICLES = hode.capi.PF_MAX_PARTICLES
 
@@ -46,9 +48,10 @@ def _check_steps(steps, T):
 class _Engine:
     """What one run and its forecasts share: the network and the settings on the device, and the loop."""
 
-    def __init__(self, model, B, N, q, sigma, link, ess, seed, method, rtol, atol, dtype, dev, store):
+    def __init__(self, model, B, N, q, sigma, link, ess, seed, method, rtol, atol, dtype, dev, store, ode_sets=False):
         nl = model.nn_residual
         self.model, self.B, self.N, self.dtype, self.dev, self.store = model, B, N, dtype, dev, store
+        self.ode_sets = ode_sets                                # particles with their own mechanistic constants
         self.H, self.L, self.method, self.rtol, self.atol = nl.hidden_dim, nl.hip_layers, method, float(rtol), float(atol)
         self.link, self.ess, self.seed = link, float(ess), int(seed)
         f64 = dict(dtype=torch.float64, device=dev)
@@ -57,7 +60,9 @@ class _Engine:
     def run(self, x, lw, ode_p, t, ins, obs, mask, idxs, counter, init_q=None):
         """Carry (x [B, N, 6], lw [B, N], ode_p [B, N, 17]) over the grid t ([T] or [B, T]) with a filter step at every index of
         `idxs` (and, with init_q, one at index 0 that spreads the particles by init_q); obs [B, T, 6] / mask uint8 [B, T, 6] or
-        None (no observations).  `counter`: the step number of the first step taken.  Returns the per-step outputs."""
+        None (no observations).  `counter`: the step number of the first step taken.  Returns the per-step outputs; the last
+        one is what `smooth()` needs on top of the history (store_particles=True, else None): (predicted [S, B, N, 6], the x_in
+        row of every step with NaN where the solve failed; log_weight_history [S, B, N]; step_dt [S, B])."""
         B, N, dev, dtype = self.B, self.N, self.dev, self.dtype
         with torch.no_grad():
             nn_flat, _ = self.model._params_on(dev)
@@ -66,6 +71,8 @@ class _Engine:
             stats = torch.empty(S, B, hode.capi.PF_COLS, dtype=torch.float64, device=dev)
             hist = torch.empty(S, B, N, 6, dtype=dtype, device=dev) if self.store else None
             ancs = torch.empty(S, B, N, dtype=torch.int32, device=dev) if self.store else None
+            kept = (torch.empty(S, B, N, 6, dtype=dtype, device=dev), torch.empty(S, B, N, dtype=torch.float64, device=dev),
+                    torch.empty(S, B, dtype=torch.float64, device=dev)) if self.store else None
             bufs = [torch.empty_like(x), torch.empty_like(x)]
             anc1 = torch.empty(B, N, dtype=torch.int32, device=dev)
             aux = [ode_p, torch.empty_like(ode_p)]
@@ -84,6 +91,10 @@ class _Engine:
                 mk = None if mask is None else mask[:, g].contiguous()
                 hode.capi.pf_step(x_in, ob, self.sigma, q, dt, lw, counter + s, seed=self.seed, id0=0, link=self.link, ess_frac=self.ess,
                                   status=status, mask=mk, aux_in=aux[0], out=out)
+                if self.store:                                  # copies only: what the step kernel was given does not change
+                    kept[0][s].copy_(x_in if status is None else torch.where((status != 0).unsqueeze(-1), nan_row[0, 0], x_in))
+                    kept[1][s].copy_(lw)
+                    kept[2][s].copy_(dt)
                 x = out[0]
                 aux.reverse()
                 s += 1
@@ -101,7 +112,7 @@ class _Engine:
                 step(sol.y[:, -1].reshape(B, N, 6).contiguous(), sol.status.view(B, N), g, dt, self.q)
                 prev = g
             x = x.clone() if self.store else x
-        return x, lw, aux[0], stats, hist, ancs
+        return x, lw, aux[0], stats, hist, ancs, kept
 
 
 class FilterResult:
@@ -113,9 +124,14 @@ class FilterResult:
       step_index [S]             the grid index of every step;  times [S] or [B, S]
       particles [B, N, 6], log_weights [B, N] (fp64, unnormalised; 0 after a resampling), ode_p [B, N, 17]: the final particles
       history [S, B, N, 6], ancestors [S, B, N] (store_particles=True): the particles after each step's gather, and the slot of
-                                 the step before that each one came from."""
+                                 the step before that each one came from;
+      predicted [S, B, N, 6], log_weight_history [S, B, N] (fp64), step_dt [S, B] (fp64) (store_particles=True): the state every
+                                 slot of the step before was carried to by the segment solve, before the noise (step 0: x0
+                                 repeated; NaN where the solve failed), the log-weights as each step left them, and each
+                                 step's dt: what `smooth()` reads."""
 
-    def __init__(self, engine, stats, step_index, times, particles, log_weights, ode_p, history, ancestors, counter):
+    def __init__(self, engine, stats, step_index, times, particles, log_weights, ode_p, history, ancestors, counter, kept=None,
+                 forecast=False):
         st = stats.permute(1, 0, 2)
         self.log_evidence_steps, self.ess = st[..., 0].contiguous(), st[..., 1].contiguous()
         self.resampled, self.alive = st[..., 2] > 0, st[..., 3].to(torch.int64)
@@ -123,7 +139,8 @@ class FilterResult:
         self.step_index, self.times = step_index, times
         self.particles, self.log_weights, self.ode_p = particles, log_weights, ode_p
         self.history, self.ancestors = history, ancestors
-        self._engine, self._counter = engine, counter
+        self.predicted, self.log_weight_history, self.step_dt = kept if kept is not None else (None, None, None)
+        self._engine, self._counter, self._forecast = engine, counter, forecast
 
     def log_evidence(self):
         """log p(all observations) per patient [B]: -inf for a patient whose particles all died (with a warning)."""
@@ -141,7 +158,9 @@ class FilterResult:
     def smoothed(self):
         """(mean, std) [B, S, 6] of the surviving lineages: the ancestor indices traced back from the last step (torch gathers),
         every lineage with its final weight.  Needs store_particles=True.  The usual caveat of genealogy smoothing applies: far
-        back from the last step few distinct ancestors are left."""
+        back from the last step few distinct ancestors are left, and the early `std` then describes that collapse, not the
+        posterior.  `smooth()` draws backward trajectories over ALL particles of every step instead; this method remains for
+        runs with `ode_sets`, which `smooth()` does not take."""
         if self.history is None:
             raise ValueError("smoothed() needs run_filter(..., store_particles=True)")
         S, B, N, _ = self.history.shape
@@ -170,10 +189,69 @@ class FilterResult:
         if not torch.equal(t[..., 0].expand_as(last), last):
             raise ValueError("t_span must start at the time of the filter's last step")
         ins = _inputs(external_inputs, e.B, T, e.dev, e.dtype)
-        x, lw, ode_p, stats, hist, ancs = e.run(self.particles, self.log_weights.clone(), self.ode_p.clone(), t, ins, None, None, idxs,
-                                                self._counter)
+        x, lw, ode_p, stats, hist, ancs, kept = e.run(self.particles, self.log_weights.clone(), self.ode_p.clone(), t, ins, None, None,
+                                                      idxs, self._counter)
         gi = torch.as_tensor(idxs, device=e.dev)
-        return FilterResult(e, stats, gi, t[..., gi], x, lw, ode_p, hist, ancs, self._counter + len(idxs))
+        return FilterResult(e, stats, gi, t[..., gi], x, lw, ode_p, hist, ancs, self._counter + len(idxs), kept, forecast=True)
+
+    def smooth(self, n_trajectories=None, seed=None):
+        """Backward-simulation smoothing (forward filtering, backward simulation): `n_trajectories` (default N) trajectories
+        per patient through the stored particles, each a draw from the joint smoothing distribution p(x_0..x_S | all
+        observations) as the particles represent it.  From a draw of the final weights backward, every step weighs ALL N
+        particles of the step before by their filter weight times the transition density to the trajectory's next state and
+        draws one (include/hode.h, "Particle smoother"; one launch of csrc/hode_smooth.hip, O(B M N S) density evaluations).
+        `seed` defaults to the filter's; the draws come from a Philox stream of their own.  Needs store_particles=True; not
+        offered on a forecast (no weighted first step) or after a run with `ode_sets` (each particle's constants are a static
+        part of its state: no particle of the step before with other constants can have led to it, and backward simulation
+        across them is not defined -- `smoothed()` remains for that case).  Returns a SmoothResult."""
+        if self.history is None or self.predicted is None:
+            raise ValueError("smooth() needs run_filter(..., store_particles=True)")
+        if self._forecast:
+            raise ValueError("smooth() is not offered on a forecast(): it has no weighted first step; smooth the run_filter result")
+        e = self._engine
+        if e.ode_sets:
+            raise ValueError("smooth() is not defined for a run with ode_sets (per-particle constants are a static part of the "
+                             "state); smoothed() traces the genealogy instead")
+        M = e.N if n_trajectories is None else int(n_trajectories)
+        if M < 1:
+            raise ValueError("n_trajectories must be at least 1")
+        idx, paths = hode.capi.pf_smooth(self.history, self.log_weight_history, self.predicted, e.q, self.step_dt, M,
+                                         seed=e.seed if seed is None else int(seed), id0=0, link=e.link)
+        return SmoothResult(paths.permute(1, 2, 0, 3).contiguous(), idx.permute(1, 2, 0).contiguous(), self.step_index, self.times)
+
+
+class SmoothResult:
+    """M backward-simulated trajectories per patient (`FilterResult.smooth`), tensors on the compute device.
+      paths [B, M, S, 6]         the trajectories, in the filter's dtype: paths[b, m, s] = history[s, b, index[b, m, s]]
+      index [B, M, S] (int32)    the slot of every step's particle; -1 (and NaN in paths) from the step backward at which no
+                                 particle could have led to the trajectory's next state (every candidate dead or impossible)
+      step_index [S], times [S] or [B, S]: the filter's
+      mean, std [B, S, 6]        fp64, equal weights over the trajectories whose index is not -1 at that step
+      lost [B]                   the number of trajectories with an index of -1 anywhere (i.e. at step 0)."""
+
+    def __init__(self, paths, index, step_index, times):
+        self.paths, self.index, self.step_index, self.times = paths, index, step_index, times
+        ok = (index >= 0).unsqueeze(-1)                                  # [B, M, S, 1]
+        n = ok.sum(1).double()                                           # [B, S, 1]
+        x = torch.where(ok, paths.double(), torch.zeros((), dtype=torch.float64, device=paths.device))
+        self.mean = x.sum(1) / n
+        d = torch.where(ok, x - self.mean.unsqueeze(1), torch.zeros((), dtype=torch.float64, device=paths.device))
+        self.std = ((d * d).sum(1) / n).sqrt()
+        self.lost = (index < 0).any(2).sum(1)
+
+    def quantile(self, q):
+        """The q-quantile(s) of every state at every step over the trajectories (lost ones left out): [B, S, 6], or
+        [len(q), B, S, 6] for a sequence q."""
+        qs = torch.as_tensor(q, dtype=torch.float64, device=self.paths.device)
+        return torch.nanquantile(self.paths.double(), qs, dim=1)
+
+    def distinct(self):
+        """[B, S] (int64): the number of distinct slots among the trajectories at every step -- what genealogy tracing loses
+        far back from the last step and backward simulation keeps."""
+        srt = self.index.sort(1).values                                   # [B, M, S]
+        new = torch.ones_like(srt, dtype=torch.bool)
+        new[:, 1:] = srt[:, 1:] != srt[:, :-1]
+        return (new & (srt >= 0)).sum(1)
 
 
 def _inputs(external_inputs, B, T, dev, dtype):
@@ -268,7 +346,7 @@ def run_filter(model, data, n_particles=1024, process_noise=0.05, noise_link="lo
         x = x0.to(dev, dtype).reshape(B, 1, 6).repeat(1, N, 1)
         lw = torch.zeros(B, N, dtype=torch.float64, device=dev)
     eng = _Engine(model, B, N, q, om.sigma, hode.capi.PF_LINK[noise_link], ess_threshold, seed, method, rtol, atol, dtype, dev,
-                  bool(store_particles))
-    x, lw, ode_p, stats, hist, ancs = eng.run(x, lw, ode_p, t, ins, obs_d, mask_d, idxs, 0, init_q=q0)
+                  bool(store_particles), ode_sets=bool(cols))
+    x, lw, ode_p, stats, hist, ancs, kept = eng.run(x, lw, ode_p, t, ins, obs_d, mask_d, idxs, 0, init_q=q0)
     gi = torch.as_tensor([0] + idxs, device=dev)
-    return FilterResult(eng, stats, gi, t[..., gi], x, lw, ode_p, hist, ancs, 1 + len(idxs))
+    return FilterResult(eng, stats, gi, t[..., gi], x, lw, ode_p, hist, ancs, 1 + len(idxs), kept)

@@ -851,6 +851,46 @@ int hode_pf_step_f64(void *stream, int B, int N, uint32_t step, uint64_t seed, u
                      double ess_frac, double *lw, double *x_out, int32_t *anc, double *stats, int n_aux, const double *aux_in,
                      double *aux_out);
 
+/* =====================================================================================================
+ * Particle smoother (inference/filter.py, FilterResult.smooth): backward-simulation smoothing (forward filtering, backward
+ * simulation) over a stored particle filter -- M trajectories per patient, each drawn from the joint smoothing distribution
+ * that the filter's particles carry, in one launch for the whole backward pass.
+ *
+ * Arguments (DEVICE unless noted): B, N, M, S, seed, id0, link on the host.  hist [S][B][N][6]: the particles after each of the
+ * S filter steps (run_filter's history); lwh [S][B][N] fp64: their log-weights as hode_pf_step left them (unnormalised, 0 after
+ * a resampling, -inf for a dead particle); pred [S][B][N][6]: pred[s][b][i] is the x_in row of step s, i.e. the state that slot
+ * i of step s - 1 was carried to by the segment solve, before the noise (pred[0] is not read; a failed solve's row is NaN);
+ * q [6] fp64 the process noise; dt [S][B] fp64 the dt of every step (dt[0] is not read); link as in hode_pf_step.
+ * Outputs: idx [S][B][M] int32, paths [S][B][M][6].
+ *
+ * Patient b draws from the Philox key id0 + b.  For trajectory m = 0..M-1, all in fp64 on the stored values, a * b + c being two
+ * roundings:
+ *  Last step.   l_i = lwh[S-1][i]; k_{S-1} is drawn as below with step number S - 1.
+ *  Steps s = S-2 .. 0.  With x~ = hist[s+1][k_{s+1}], sg_j = q_j * sqrt(dt[s+1][b]), r_j = 1 / sg_j and p = pred[s+1][i]:
+ *     l_i = lwh[s][i] + T,  T = the sum over j = 0..5 (from 0, in order) of tau_j,
+ *       sg_j > 0:       tau_j = -0.5 * (z * z);  additive link z = (x~_j - p_j) * r_j;
+ *                       log link z = (log x~_j - (log p_j - 0.5 * (sg_j * sg_j))) * r_j
+ *                       (which is (log x~_j - log p_j + sg_j^2 / 2) / sg_j; the candidate's bracket is formed once);
+ *       otherwise:      the transition is a point mass: tau_j = 0 if p_j == x~_j exactly (as stored values), else -inf.
+ *     A non-finite l_i counts as -inf: a NaN pred row, a dead particle, the logarithm of a non-positive number.  Terms that
+ *     are the same for every i are dropped.
+ *  Draw.  mx = max_i l_i, w_i = exp(l_i - mx) (0 for -inf), c_k = the SEQUENTIAL running sum of w over i = 0..k,
+ *     u = u01(word x of the block (group m, tag 10, step s)), k_s = min{k : c_k >= u * c_{N-1}}, moved back to the nearest k
+ *     with w_k > 0 (hode_pf_step's rule; on a sequential sum the minimum already has w_k > 0).  No candidate alive:
+ *     idx = -1 and paths = NaN for this step and every earlier one of that trajectory.
+ *  Outputs.  idx[s][b][m] = k_s, paths[s][b][m] = hist[s][b][k_s].
+ *
+ * The same call gives the same bits, and a trajectory's bits depend on (seed, id0 + b, m) and the patient's stored data only:
+ * not on M, on B or on how the launch is cut.  The kernel computes both instantiations in fp64 (there is no fp32 pair loop).
+ *
+ * HODE_EINVAL (nothing launched): B, N, M or S < 1, link not 0 or 1, a NULL pointer.  HODE_EUNSUPPORTED:
+ * N > HODE_PF_MAX_PARTICLES (a bad argument outranks it), or B * ceil(M / 256) >= 2^31; M itself is not bounded.
+ * ===================================================================================================== */
+int hode_pf_smooth_f32(void *stream, int B, int N, int M, int S, uint64_t seed, uint32_t id0, const float *hist, const double *lwh,
+                       const float *pred, const double *q, const double *dt, int link, int32_t *idx, float *paths);
+int hode_pf_smooth_f64(void *stream, int B, int N, int M, int S, uint64_t seed, uint32_t id0, const double *hist, const double *lwh,
+                       const double *pred, const double *q, const double *dt, int link, int32_t *idx, double *paths);
+
 #ifdef __cplusplus
 }
 #endif
