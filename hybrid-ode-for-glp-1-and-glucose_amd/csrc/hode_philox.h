@@ -30,6 +30,9 @@ constexpr uint32_t kRngFilterNoise = 8, kRngFilterResample = 9;
 // backward simulation over a stored filter (hode_smooth.hip): the step whose slot is drawn as the iteration, the trajectory m
 // as the group, one uniform per draw
 constexpr uint32_t kRngFilterSmooth = 10;
+// the parameter move of the particle filter (hode_pf_params.hip): the patient's key as the chain, the filter step as the
+// iteration; group 5 i + (k >> 2) gives particle i the normals of its payload columns 4 (k >> 2) .. 4 (k >> 2) + 3
+constexpr uint32_t kRngFilterParam = 11;
 
 struct Philox4 { uint32_t x, y, z, w; };
 

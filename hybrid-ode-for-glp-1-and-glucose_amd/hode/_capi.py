@@ -34,7 +34,8 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_pred_loo_fold_f32", "hode_pred_loo_fold_f64", "hode_pred_loo_finish_f32", "hode_pred_loo_finish_f64",
            "hode_pop_params_f32", "hode_pop_params_f64", "hode_pop_grad_f32", "hode_pop_grad_f64",
            "hode_x0_params_f32", "hode_x0_params_f64", "hode_x0_grad_f32", "hode_x0_grad_f64",
-           "hode_pf_step_f32", "hode_pf_step_f64", "hode_pf_smooth_f32", "hode_pf_smooth_f64"]
+           "hode_pf_step_f32", "hode_pf_step_f64", "hode_pf_smooth_f32", "hode_pf_smooth_f64",
+           "hode_pf_params_f32", "hode_pf_params_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -529,6 +530,41 @@ def pf_smooth(hist, lwh, pred, q, dt, M, seed=0, id0=0, link=1, out=None):
         C.c_uint32(int(id0) & 0xFFFFFFFF), _ptr(hist), _ptr(lwh), _ptr(pred), _ptr(q), _ptr(dt), C.c_int(int(link)), _ptr(idx),
         _ptr(paths)), "hode_pf_smooth")
     return idx, paths
+
+
+PF_MOVE = {"carried": 0, "identity": 1, "log": 2}
+
+
+def pf_params(lw, aux, mode, walk, dt, step, shrink, seed=0, id0=0, out=None):
+    """The parameter move of the particle filter (include/hode.h "Particle filter: parameter move"), after a pf_step: lw fp64
+    [B, N] as the step left it (read only), aux [B, N, n_aux] fp32 or fp64 (1 <= n_aux <= 17) MOVED IN PLACE, mode int32 [n_aux]
+    (PF_MOVE: 0 carried, 1 identity link, 2 log link), walk fp64 [n_aux] and dt fp64 [B], all on the device; shrink in [0, 1].
+    `out`: a pstats buffer to write into (a loop reuses it), else it is allocated.
+    Returns pstats fp64 [B, 2 * n_aux]: (mean, variance) in link space of every selected column before the move, NaN otherwise."""
+    _need_gpu(aux)
+    if aux.dim() != 3 or not aux.is_contiguous() or not 1 <= aux.shape[2] <= PF_MAX_AUX:
+        raise HodeError(f"pf_params: aux must be a contiguous [B, N, n_aux] with 1 <= n_aux <= {PF_MAX_AUX}")
+    B, N, n_aux = (int(v) for v in aux.shape)
+    dev = aux.device
+    if N > PF_MAX_PARTICLES:
+        raise HodeError(f"pf_params: N = {N} particles, the kernel takes up to {PF_MAX_PARTICLES} (HODE_PF_MAX_PARTICLES)")
+    for name, v, n in (("lw", lw, B * N), ("walk", walk, n_aux), ("dt", dt, B)):
+        if v.dtype != torch.float64 or v.device != dev or v.numel() != n or not v.is_contiguous():
+            raise HodeError(f"pf_params: {name} must be a contiguous fp64 device tensor of {n} elements")
+    if mode.dtype != torch.int32 or mode.device != dev or mode.numel() != n_aux or not mode.is_contiguous():
+        raise HodeError(f"pf_params: mode must be a contiguous int32 device tensor of {n_aux} elements")
+    shrink = float(shrink)
+    if not 0.0 <= shrink <= 1.0:
+        raise HodeError("pf_params: shrink must lie in [0, 1]")
+    if out is None:
+        out = torch.empty(B, 2 * n_aux, dtype=torch.float64, device=dev)
+    if out.dtype != torch.float64 or out.device != dev or out.numel() != 2 * B * n_aux or not out.is_contiguous():
+        raise HodeError("pf_params: out must be a contiguous fp64 [B, 2 * n_aux] on aux's device")
+    _check(getattr(load(), f"hode_pf_params_{_sfx(aux.dtype)}")(
+        _stream(), C.c_int(B), C.c_int(N), C.c_uint32(int(step) & 0xFFFFFFFF), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+        C.c_uint32(int(id0) & 0xFFFFFFFF), _ptr(lw), C.c_int(n_aux), _ptr(aux), _ptr(mode), _ptr(walk), _ptr(dt), C.c_double(shrink),
+        _ptr(out)), "hode_pf_params")
+    return out
 
 
 PRED_MAX_BINS, PRED_FIXED_COLS, PRED_SCORE_BLOCKS = 32, 16, 128

@@ -20,7 +20,7 @@ import os
 import sys
 
 from .calibrate import CalibrationResult, fit_patients
-from .filter import FilterResult, SmoothResult, run_filter
+from .filter import FilterResult, LearnedParameters, ParameterLearning, SmoothResult, run_filter
 from .initial_state import InitialStatePrior, LatentStateResult
 from .population import PopulationResult, run_population
 from .predictive import LooResult, PredictiveAccumulator, PredictiveSummary, compare, loo_tail_size, predictive_summary, tail_size
@@ -30,7 +30,7 @@ from .vi import VariationalInference
 __all__ = ["VariationalInference", "fit_patients", "CalibrationResult", "run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results",
            "sobol_study", "sobol_indices", "saltelli_design", "SobolIndices", "PredictiveAccumulator", "PredictiveSummary", "predictive_summary",
            "tail_size", "loo_tail_size", "LooResult", "compare", "run_population", "PopulationResult", "InitialStatePrior",
-           "LatentStateResult", "run_filter", "FilterResult", "SmoothResult"]
+           "LatentStateResult", "run_filter", "FilterResult", "SmoothResult", "ParameterLearning", "LearnedParameters"]
 
 _MCMC_NAMES = ("run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results")
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -891,6 +891,52 @@ int hode_pf_smooth_f32(void *stream, int B, int N, int M, int S, uint64_t seed, 
 int hode_pf_smooth_f64(void *stream, int B, int N, int M, int S, uint64_t seed, uint32_t id0, const double *hist, const double *lwh,
                        const double *pred, const double *q, const double *dt, int link, int32_t *idx, double *paths);
 
+/* =====================================================================================================
+ * Particle filter: parameter move (inference/filter.py, run_filter(learn=...)): Liu & West's kernel shrinkage and / or a random
+ * walk on chosen columns of the payload rows, so that a filter whose particles carry their own constants learns them online
+ * instead of collapsing onto the rows it started with.  Launched after hode_pf_step_*: it reads the log-weights the step left
+ * and moves, in place, the aux rows the step gathered.
+ *
+ * Arguments (DEVICE unless noted): B, N, step, seed, id0, n_aux, shrink on the host.  lw [B*N] fp64, read only; aux [B*N][n_aux],
+ * 1 <= n_aux <= HODE_PF_MAX_AUX, IN/OUT; mode [n_aux] int32: HODE_PF_MOVE_CARRIED (0) the column is carried, HODE_PF_MOVE_IDENTITY
+ * (1) it is selected with phi = theta, HODE_PF_MOVE_LOG (2) selected with phi = log theta (any other value: carried); walk [n_aux]
+ * fp64, a standard deviation per sqrt(time) in link space (only its square is used); dt [B] fp64; shrink = a in [0, 1];
+ * pstats [B][2 * n_aux] fp64.  Layout and launch as hode_pf_step_*: one workgroup of 256 lanes per patient, the patient's N
+ * weights (fp64) in LDS.
+ *
+ * For patient b, everything in fp64, a * b + c being two roundings, every sum over the particles in the order of the step
+ * kernel's sums (lane t adds its particles t, t + 256, ... in order from 0.0; a butterfly inside each wave of 64; then
+ * (wave 0 + wave 1) + (wave 2 + wave 3)):
+ *  Counting.  Particle i counts iff lw_i > -inf (false for NaN) and, for every selected column k, (double) aux[i][k] is finite
+ *     and, under the log link, > 0 -- judged on the rows as they came in.  m = the maximum of lw over the particles that count;
+ *     w_i = exp(lw_i - m), sw = sum w.  No particle counts (or m = +inf, of which no weights can be formed): pstats[b] is NaN
+ *     in all 2 * n_aux entries and nothing is moved.
+ *  Moments, per selected column k.  phi_i = (double) aux[i][k] or its log; mean = (sum w_i * phi_i) / sw;
+ *     var = (sum w_i * (d_i * d_i)) / sw with d_i = phi_i - mean.  pstats[b][2k] = mean, pstats[b][2k + 1] = var: the cloud
+ *     before the move.  A carried column has NaN in both.
+ *  Move, per selected column k unless a == 1 and walk_k == 0 (then the column keeps its bits):
+ *     sd = sqrt((1 - a * a) * var + (walk_k * walk_k) * dt_b);
+ *     eps = element k & 3 of the four normals (Box-Muller, as the samplers') of the block (group 5 i + (k >> 2), tag 11, step);
+ *     phi' = (mean + a * (phi_i - mean)) + sd * eps;  aux[i][k] = (R) phi' or (R) exp(phi'), rounded once.
+ *     Rows that do not count and carried columns keep their bits.
+ * With a = (3 delta - 1) / (2 delta) and walk = 0 this is Liu & West's (2001) shrinkage for the discount delta: it keeps the
+ * weighted mean and variance of the cloud in expectation.  a = 1 with walk > 0 is a random walk.
+ *
+ * A draw is keyed by what is drawn -- (seed, id0 + b, step, particle, column) -- and depends neither on which other columns
+ * are selected nor on B or the launch.  The same call gives the same bits, and a patient's bits depend on its key id0 + b only.
+ *
+ * HODE_EINVAL (nothing launched): B < 1, N < 1, n_aux outside 1..HODE_PF_MAX_AUX, shrink outside [0, 1] or NaN, a NULL among
+ * lw, aux, mode, walk, dt, pstats.  HODE_EUNSUPPORTED: N > HODE_PF_MAX_PARTICLES (a bad argument outranks it).  mode and walk
+ * live on the device and are not validated here: the caller does.
+ * ===================================================================================================== */
+#define HODE_PF_MOVE_CARRIED 0
+#define HODE_PF_MOVE_IDENTITY 1
+#define HODE_PF_MOVE_LOG 2
+int hode_pf_params_f32(void *stream, int B, int N, uint32_t step, uint64_t seed, uint32_t id0, const double *lw, int n_aux, float *aux,
+                       const int32_t *mode, const double *walk, const double *dt, double shrink, double *pstats);
+int hode_pf_params_f64(void *stream, int B, int N, uint32_t step, uint64_t seed, uint32_t id0, const double *lw, int n_aux, double *aux,
+                       const int32_t *mode, const double *walk, const double *dt, double shrink, double *pstats);
+
 #ifdef __cplusplus
 }
 #endif
