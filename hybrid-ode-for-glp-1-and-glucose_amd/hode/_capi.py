@@ -35,7 +35,7 @@ SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_
            "hode_pop_params_f32", "hode_pop_params_f64", "hode_pop_grad_f32", "hode_pop_grad_f64",
            "hode_x0_params_f32", "hode_x0_params_f64", "hode_x0_grad_f32", "hode_x0_grad_f64",
            "hode_pf_step_f32", "hode_pf_step_f64", "hode_pf_smooth_f32", "hode_pf_smooth_f64",
-           "hode_pf_params_f32", "hode_pf_params_f64"]
+           "hode_pf_params_f32", "hode_pf_params_f64", "hode_ukf_step_f32", "hode_ukf_step_f64"]
 
 INPUT_KEYS = ("meal", "tVNS", "GD")
 
@@ -565,6 +565,77 @@ def pf_params(lw, aux, mode, walk, dt, step, shrink, seed=0, id0=0, out=None):
         C.c_uint32(int(id0) & 0xFFFFFFFF), _ptr(lw), C.c_int(n_aux), _ptr(aux), _ptr(mode), _ptr(walk), _ptr(dt), C.c_double(shrink),
         _ptr(out)), "hode_pf_params")
     return out
+
+
+UKF_COLS = 16
+UKF_STATS = ("log_evidence", "nis", "n_seen", "alive")            # stats columns 0..3; 4..9 the means, 10..15 the variances
+
+
+def ukf_weights(n, alpha=1.0, beta=0.0, kappa=1.0):
+    """(gamma, wm0, wc0, wi) of the scaled unscented transform in n dimensions: lambda = alpha^2 (n + kappa) - n,
+    gamma = sqrt(n + lambda), the centre point's weights wm0 = lambda / (n + lambda) for the mean and wc0 = wm0 + 1 - alpha^2 + beta
+    for the covariance, every other point's wi = 1 / (2 (n + lambda))."""
+    n, alpha, beta, kappa = int(n), float(alpha), float(beta), float(kappa)
+    lam = alpha * alpha * (n + kappa) - n
+    if not n + lam > 0.0:
+        raise HodeError(f"ukf_weights: n + lambda = {n + lam} must be positive (alpha = {alpha}, kappa = {kappa}, n = {n})")
+    wm0 = lam / (n + lam)
+    return (n + lam) ** 0.5, wm0, wm0 + 1.0 - alpha * alpha + beta, 1.0 / (2.0 * (n + lam))
+
+
+def ukf_step(x_in, aux_in, mode, obs, sigma, q, walk, dt, alive, mean, cov, weights, predict=True, link=1, status=None, mask=None,
+             out=None):
+    """One step of the unscented Kalman filter (include/hode.h "Unscented Kalman filter"): x_in [B, K, 6] fp32 or fp64 on the
+    device and aux_in [B, K, 17] of its dtype (the solve's output rows and the ode_p rows they were solved with), K = 2 (6 + P) + 1;
+    mode: 17 ints on the HOST (PF_MOVE: 0 carried, 1 identity link, 2 log link), P of them non-zero; obs [B, 6] (NaN = missing),
+    mask uint8 [B, 6] or None, status int32 [B, K] or None; sigma / q fp64 [6], walk fp64 [17], dt fp64 [B] on the device;
+    alive int32 [B], mean fp64 [B, n] and cov fp64 [B, n, n] UPDATED IN PLACE (mean and cov are read only with predict=False);
+    weights = (gamma, wm0, wc0, wi), e.g. ukf_weights(n).  `out`: (x_out, aux_out, stats) buffers to write into (a loop reuses
+    them), else they are allocated.  Returns (x_out [B, K, 6], aux_out [B, K, 17], stats fp64 [B, 16])."""
+    _need_gpu(x_in)
+    mode = [int(v) for v in (mode.tolist() if hasattr(mode, "tolist") else mode)]
+    if len(mode) != PF_MAX_AUX or any(v not in (0, 1, 2) for v in mode):
+        raise HodeError(f"ukf_step: mode must be {PF_MAX_AUX} host integers in 0..2 (PF_MOVE)")
+    n = 6 + sum(1 for v in mode if v)
+    K = 2 * n + 1
+    if x_in.dim() != 3 or tuple(x_in.shape[1:]) != (K, 6) or not x_in.is_contiguous():
+        raise HodeError(f"ukf_step: x_in must be a contiguous [B, K, 6] with K = 2 (6 + P) + 1 = {K}")
+    B = int(x_in.shape[0])
+    dev, dt_ = x_in.device, x_in.dtype
+    if tuple(aux_in.shape) != (B, K, PF_MAX_AUX) or aux_in.dtype != dt_ or aux_in.device != dev or not aux_in.is_contiguous():
+        raise HodeError(f"ukf_step: aux_in must be a contiguous [B, K, {PF_MAX_AUX}] of x_in's dtype")
+    obs = obs.to(device=dev, dtype=dt_).contiguous()
+    if obs.numel() != 6 * B:
+        raise HodeError("ukf_step: obs must be [B, 6]")
+    for name, v, m in (("sigma", sigma, 6), ("q", q, 6), ("walk", walk, PF_MAX_AUX), ("dt", dt, B), ("mean", mean, B * n),
+                       ("cov", cov, B * n * n)):
+        if v.dtype != torch.float64 or v.device != dev or v.numel() != m or not v.is_contiguous():
+            raise HodeError(f"ukf_step: {name} must be a contiguous fp64 device tensor of {m} elements")
+    if alive.dtype != torch.int32 or alive.device != dev or alive.numel() != B or not alive.is_contiguous():
+        raise HodeError(f"ukf_step: alive must be a contiguous int32 device tensor of {B} elements")
+    if mask is not None:
+        mask = mask.to(device=dev).contiguous()
+        if mask.dtype != torch.uint8 or mask.numel() != 6 * B:
+            raise HodeError("ukf_step: mask must be uint8 [B, 6]")
+    if status is not None:
+        status = status.to(device=dev).contiguous()
+        if status.dtype != torch.int32 or status.numel() != B * K:
+            raise HodeError("ukf_step: status must be int32 [B, K]")
+    gamma, wm0, wc0, wi = (float(v) for v in weights)
+    if out is None:
+        out = (torch.empty_like(x_in), torch.empty_like(aux_in), torch.empty(B, UKF_COLS, dtype=torch.float64, device=dev))
+    x_out, aux_out, stats = out
+    if (x_out.shape != x_in.shape or x_out.dtype != dt_ or x_out.device != dev or not x_out.is_contiguous()
+            or aux_out.shape != aux_in.shape or aux_out.dtype != dt_ or aux_out.device != dev or not aux_out.is_contiguous()
+            or stats.dtype != torch.float64 or stats.device != dev or stats.numel() != B * UKF_COLS or not stats.is_contiguous()):
+        raise HodeError("ukf_step: out must be (x_out like x_in, aux_out like aux_in, stats fp64 [B, 16]), contiguous")
+    if x_out.data_ptr() == x_in.data_ptr() or aux_out.data_ptr() == aux_in.data_ptr():
+        raise HodeError("ukf_step: x_out may not alias x_in, aux_out may not alias aux_in")
+    _check(getattr(load(), f"hode_ukf_step_{_sfx(dt_)}")(
+        _stream(), C.c_int(B), C.c_int(1 if predict else 0), C.c_int(int(link)), (C.c_int32 * PF_MAX_AUX)(*mode), C.c_double(gamma),
+        C.c_double(wm0), C.c_double(wc0), C.c_double(wi), _ptr(x_in), _ptr(status), _ptr(aux_in), _ptr(obs), _ptr(mask), _ptr(sigma),
+        _ptr(q), _ptr(walk), _ptr(dt), _ptr(alive), _ptr(mean), _ptr(cov), _ptr(x_out), _ptr(aux_out), _ptr(stats)), "hode_ukf_step")
+    return x_out, aux_out, stats
 
 
 PRED_MAX_BINS, PRED_FIXED_COLS, PRED_SCORE_BLOCKS = 32, 16, 128

@@ -399,6 +399,37 @@ def _inputs(external_inputs, B, T, dev, dtype):
     return ins
 
 
+def _check_data(data):
+    """The shapes of a batch dict, checked on the host: (initial_state [B, 6], time_points [T] or [B, T], observations
+    [B, T, 6], B, T)."""
+    x0 = torch.as_tensor(data["initial_state"])
+    if x0.dim() != 2 or x0.shape[1] != 6:
+        raise ValueError("initial_state must be [B, 6]")
+    B = int(x0.shape[0])
+    t = torch.as_tensor(data["time_points"])
+    T = int(t.shape[-1])
+    if t.dim() not in (1, 2) or T < 2 or (t.dim() == 2 and t.shape[0] != B):
+        raise ValueError("time_points must be [T] or [B, T] with T >= 2")
+    obs = torch.as_tensor(data["observations"])
+    if tuple(obs.shape) != (B, T, 6):
+        raise ValueError(f"observations must be [B, T, 6] = ({B}, {T}, 6)")
+    return x0, t, obs, B, T
+
+
+def _observed_at(obs_d, mask_d):
+    """[T] bool on the device: the grid points at which any patient has an observed entry."""
+    seen = torch.isfinite(obs_d) if mask_d is None else mask_d.bool()
+    return seen.any(2).any(0)
+
+
+def _default_steps(obs_d, mask_d):
+    """The filter steps when none are given: the later grid points at which any patient has an observed entry, plus the last."""
+    at = _observed_at(obs_d, mask_d)
+    at[-1] = True
+    at[0] = False
+    return torch.nonzero(at).reshape(-1).tolist()
+
+
 def run_filter(model, data, n_particles=1024, process_noise=0.05, noise_link="log", noise_sigma=1.0, initial_spread=0.1, ode_sets=None,
                ess_threshold=0.5, steps=None, seed=0, solver="dopri5", rtol=1e-6, atol=1e-8, dtype=torch.float32, store_particles=False,
                learn=None):
@@ -430,17 +461,7 @@ def run_filter(model, data, n_particles=1024, process_noise=0.05, noise_link="lo
     if om.marginal:
         raise ValueError('run_filter weights under a fixed observation noise: noise="marginal" is not offered here')
     method = _method(solver)
-    x0 = torch.as_tensor(data["initial_state"])
-    if x0.dim() != 2 or x0.shape[1] != 6:
-        raise ValueError("initial_state must be [B, 6]")
-    B = int(x0.shape[0])
-    t = torch.as_tensor(data["time_points"])
-    T = int(t.shape[-1])
-    if t.dim() not in (1, 2) or T < 2 or (t.dim() == 2 and t.shape[0] != B):
-        raise ValueError("time_points must be [T] or [B, T] with T >= 2")
-    obs = torch.as_tensor(data["observations"])
-    if tuple(obs.shape) != (B, T, 6):
-        raise ValueError(f"observations must be [B, T, 6] = ({B}, {T}, 6)")
+    x0, t, obs, B, T = _check_data(data)
     if learn is not None and not isinstance(learn, ParameterLearning):
         raise ValueError(f"learn must be a ParameterLearning or None, not {type(learn).__name__}")
     cols = {}
@@ -460,15 +481,10 @@ def run_filter(model, data, n_particles=1024, process_noise=0.05, noise_link="lo
     obs_d = om.obs.view(B, T, 6)
     mask_d = None if om.mask is None else om.mask.view(B, T, 6)
     observed = None
-    if idxs is None or learn is not None:
-        seen = torch.isfinite(obs_d) if mask_d is None else mask_d.bool()
-        at = seen.any(2).any(0)
-        if learn is not None:
-            observed = at.tolist()                                      # (a learning run's own read-back, before the loop)
+    if learn is not None:
+        observed = _observed_at(obs_d, mask_d).tolist()                 # (a learning run's own read-back, before the loop)
     if idxs is None:
-        at[T - 1] = True
-        at[0] = False
-        idxs = torch.nonzero(at).reshape(-1).tolist()                   # the one read-back, before the loop
+        idxs = _default_steps(obs_d, mask_d)                            # the one read-back, before the loop
     t = t.to(dev, dtype)
     ins = _inputs(data.get("external_inputs"), B, T, dev, dtype)
     with torch.no_grad():

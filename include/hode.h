@@ -937,6 +937,76 @@ int hode_pf_params_f32(void *stream, int B, int N, uint32_t step, uint64_t seed,
 int hode_pf_params_f64(void *stream, int B, int N, uint32_t step, uint64_t seed, uint32_t id0, const double *lw, int n_aux, double *aux,
                        const int32_t *mode, const double *walk, const double *dt, double shrink, double *pstats);
 
+/* =====================================================================================================
+ * Unscented Kalman filter (inference/ukf.py, run_ukf): one step of a sigma-point Kalman filter per patient -- the unscented
+ * mean and covariance of the propagated points, the redraw, the measurement update under the observation model and the points
+ * for the next solve -- i.e. everything between two forward solves of the B * K sigma-point trajectories.  Deterministic: there
+ * is no seed.
+ *
+ * Sizes and layout.  P = the number of non-zero entries of mode [17] (0 <= P <= 17), n = 6 + P, K = 2 n + 1 (13 <= K <= 47).
+ * Coordinates 0..5 are the states, 6..n-1 the learned columns of the ode_p row in ascending column order.  Patient-major:
+ * sigma point k of patient b is row b * K + k.  One wave of 64 lanes per patient, four patients per workgroup of 256 lanes; a
+ * patient's working set (fp64) lives in LDS, 2.8 KB at n = 6 and 21.3 KB at n = 23, sized by n at launch.
+ *
+ * Arguments (DEVICE unless noted): B, predict (0 / 1), link (HODE_PF_LINK_ADD / _LOG, for the states) on the host;
+ * mode [17] int32 on the HOST, the hode_pf_params encoding (HODE_PF_MOVE_CARRIED 0, _IDENTITY 1, _LOG 2): the ABI validates it
+ * and sizes the launch from it, and the kernel receives the columns by value -- there is no device copy that could disagree;
+ * gamma, wm0, wc0, wi fp64 on the host: the spread and the weights of the unscented transform (centre point wm0 / wc0 for
+ * the mean / the covariance, every other point wi for both); x_in [B*K][6] the solve's output rows; status [B*K] int32 or NULL;
+ * aux_in [B*K][17] the ode_p row every sigma point was solved with; obs [B][6]; mask [B][6] uint8 or NULL; sigma [6], q [6],
+ * walk [17] fp64 (observation noise, process noise of the states, random-walk sd of the learned constants per sqrt(time));
+ * dt [B] fp64; alive [B] int32 IN/OUT (0 = the patient is lost); mean [B][n], cov [B][n][n] fp64, read only when predict == 0,
+ * always written; x_out [B*K][6], aux_out [B*K][17] the sigma points and their ode_p rows for the next solve;
+ * stats [B][HODE_UKF_COLS] fp64.
+ *
+ * Everything below is computed in fp64 and rounded once on store; a * b + c is two roundings; every sum over the points k runs
+ * from 0.0 over k = 0, 1, .. in order with the weight multiplied first (acc += w_k * term).  g is the state link (log or
+ * identity), phi_c the link of learned column c.
+ *  a. Predict (predict == 1).  zeta_k = (g(x_in[k]), phi(aux_in[k][cols])); m- = sum wm_k zeta_k;
+ *     P- = sum wc_k (zeta_k - m-)(zeta_k - m-)^T + diag(s^2), s_j^2 = (q_j q_j) dt_b for a state and (walk_c walk_c) dt_b for a
+ *     learned column; then, under the log link, m-_j -= 0.5 s_j^2 for every state j (the drift that keeps the mean: exactly
+ *     hode_pf_step's state model).  The patient is lost if a row has status != 0, or a state or a learned value that is not
+ *     finite, or not positive under a log link.  With predict == 0, (m-, P-) are read from mean, cov; status, dt, q and walk are
+ *     not read, x_in only to copy a lost patient's rows, and row b * K of aux_in supplies the carried columns.
+ *  b. Redraw.  L = the lower Cholesky factor of P-, column by column without pivoting: pivot_j = P-_jj - sum_{k<j} L_jk^2,
+ *     L_jj = sqrt(pivot_j), L_ij = (P-_ij - sum_{k<j} L_ik L_jk) / L_jj.  A pivot <= n 2^-52 |P-_jj| gives a zero column (so a
+ *     coordinate with zero spread stays exact, and an all-zero covariance gives K equal points); a non-finite pivot loses the
+ *     patient.  chi_0 = m-, chi_i = m- + gamma L[:, i-1], chi_{n+i} = m- - gamma L[:, i-1], i = 1..n.
+ *  c. Update.  J = the seen states: obs_j finite and, with a mask, the mask byte set (no arithmetic touches an unseen obs_j);
+ *     d = |J|.  Y_k = g^-1(chi_k) on J; yh = sum wm_k Y_k; S = sum wc_k (Y_k - yh)(Y_k - yh)^T + diag(sigma_J sigma_J);
+ *     C = sum wc_k (chi_k - m-)(Y_k - yh)^T; r = obs_J - yh.  Through the Cholesky factor L_S of S (plain: a pivot that is not
+ *     positive and finite loses the patient): z = L_S^-1 r, W = C L_S^-T (forward substitution, row by row), which makes the gain
+ *     K_g = W L_S^-1; m = m- + W z (= m- + K_g r); P = P- - W W^T (= P- - K_g S K_g^T), symmetrised as 0.5 (P_ij + P_ji);
+ *     NIS = z^T z (= r^T S^-1 r); log det S = 2 sum log L_S,aa; increment = -0.5 ((NIS + log det S) + d log 2 pi).
+ *     With d == 0 the increment is exactly 0, NIS is 0 and m = m-, P = P- bit for bit.
+ *  d. Emit.  New points from (m, P) as in (b); x_out[k] = g^-1(state part); aux_out[k] = row b * K of aux_in with the learned
+ *     columns replaced by phi^-1(parameter part); mean = m, cov = P.  A non-finite pivot or a non-finite emitted value loses
+ *     the patient.  x_out may not alias x_in, aux_out may not alias aux_in.
+ *  e. stats: [0] the evidence increment, [1] NIS, [2] d, [3] alive after the step (1 / 0), [4..9] the unscented mean of the
+ *     natural-space states of the emitted points, sum wm_k x_k, [10..15] their variance, sum wc_k (x_k - mean)^2 (both on the
+ *     fp64 values, before the rounding of the store).
+ *
+ * A lost patient (alive == 0 on entry, or lost in a..d): alive = 0; stats[0] = -inf, [2] = d, [3] = 0, the rest NaN; mean and
+ * cov NaN; x_out = x_in and aux_out = aux_in copied (hode_pf_step's rule for a dead patient).  It stays lost; the other
+ * patients are untouched.
+ *
+ * There are no atomics and every sum runs in a fixed order: the same call gives the same bits, and a patient's bits depend
+ * neither on B nor on its row.
+ *
+ * HODE_EINVAL (nothing launched): B < 1, predict not 0 or 1, link not 0 or 1, a mode value outside 0..2, gamma not finite or
+ * not positive, a non-finite wm0, wc0 or wi, a NULL among mode, x_in, aux_in, obs, sigma, q, walk, dt, alive, mean, cov, x_out,
+ * aux_out, stats, x_out == x_in, aux_out == aux_in.  HODE_EUNSUPPORTED: never (n <= 23 always holds).
+ * ===================================================================================================== */
+#define HODE_UKF_COLS 16
+int hode_ukf_step_f32(void *stream, int B, int predict, int link, const int32_t *mode, double gamma, double wm0, double wc0, double wi,
+                      const float *x_in, const int32_t *status, const float *aux_in, const float *obs, const uint8_t *mask,
+                      const double *sigma, const double *q, const double *walk, const double *dt, int32_t *alive, double *mean,
+                      double *cov, float *x_out, float *aux_out, double *stats);
+int hode_ukf_step_f64(void *stream, int B, int predict, int link, const int32_t *mode, double gamma, double wm0, double wc0, double wi,
+                      const double *x_in, const int32_t *status, const double *aux_in, const double *obs, const uint8_t *mask,
+                      const double *sigma, const double *q, const double *walk, const double *dt, int32_t *alive, double *mean,
+                      double *cov, double *x_out, double *aux_out, double *stats);
+
 #ifdef __cplusplus
 }
 #endif
