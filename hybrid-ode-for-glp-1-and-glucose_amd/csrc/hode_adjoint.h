@@ -1,7 +1,7 @@
 // hode_adjoint.h -- backward (VJP) building blocks of the tuned path: the transposed-matrix LDS image and its products, one hidden
 // layer backward, the edge-parameter policies and flushes, mech_vjp, input_vjp, rhs_vjp.
-// Used by: hode_solve_bwd.hip (K4 adjoint, K5 RHS backward), hode_solve_bwd_ws.hip, hode_generic.hip (mech_vjp, input_vjp),
-// lab/hode_solve_bwd_split.hip.  No forward kernel includes it.
+// Used by: hode_solve_bwd.hip (K4 adjoint, K5 RHS backward), hode_solve_bwd_ws.hip, hode_generic_vjp.h and
+// hode_generic_bwd_multi.hip (mech_vjp, input_vjp), lab/hode_solve_bwd_split.hip.  No forward kernel includes it.
 #pragma once
 #include "hode_rhs_eval.h"
 #ifdef HODE_LAB

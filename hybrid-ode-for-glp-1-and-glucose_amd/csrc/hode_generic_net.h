@@ -1,6 +1,7 @@
-// hode_generic_net.h -- what the kernels of the GENERIC network path share about a network (hode_generic.hip: K1 .. K5;
-// hode_generic_jvp.hip: K6): the derivative of an activation from its taped value, the flat parameter layout, the LDS image of
-// the edge parameters, and the skewed LDS activation vector with its chunked weight loads.
+// hode_generic_net.h -- what the kernels of the GENERIC network path share about a network (K1 .. K5: hode_generic_rhs.h and
+// hode_generic_vjp.h with the sources that include them, hode_generic_bwd_multi.hip; K6: hode_generic_jvp.hip): the derivative of
+// an activation from its taped value, the flat parameter layout, the LDS image of the edge parameters, and the skewed LDS
+// activation vector with its chunked weight loads.
 #pragma once
 #include "hode_xlane.h"
 #include "../../include/hode.h"

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/hode.h"
 
 namespace hode {
@@ -39,6 +40,11 @@ template <typename R> struct AdjArgs {
 template <typename R> struct AdjInArgs : AdjArgs<R> {
     R *gmeal, *gtvns, *ggd;
 };
+// the argument block of an adjoint kernel template with a GIN flag (solve_bwd_kernel, solve_bwd_generic_kernel), and the gradient
+// row of input q (0 meal, 1 tVNS, 2 GD) in either block
+template <typename R, bool GIN> using AdjArgsT = std::conditional_t<GIN, AdjInArgs<R>, AdjArgs<R>>;
+template <typename R> __device__ __forceinline__ R *gin_row(const AdjArgs<R> &, int) { return nullptr; }
+template <typename R> __device__ __forceinline__ R *gin_row(const AdjInArgs<R> &a, int q) { return (q == 0) ? a.gmeal : (q == 1) ? a.gtvns : a.ggd; }
 
 // tangent-linear pass over the tape (hode_solve_jvp.hip).  The external inputs are not arguments: the tape holds what the
 // stages used (activations, stage state, the step's interval constants); gd_mode selects the Hill-term instantiation.
@@ -84,11 +90,15 @@ template <typename R> int launch_solve_jvp(hipStream_t s, const JvpArgs<R> &a, i
 template <typename R> int launch_solve_jvp_generic(hipStream_t s, const JvpArgs<R> &a, int L, int act, int method);
 template <typename R> int launch_rhs_fwd(hipStream_t s, const RhsArgs<R> &a, int L);
 template <typename R> int launch_rhs_bwd(hipStream_t s, const RhsArgs<R> &a, int L);
-// generic network path (hode_generic.hip): H <= 128, L <= 8, weights streamed from L2
+// generic network path: H <= 128, L <= 8, weights streamed from L2.  Forward (hode_generic.hip):
 template <typename R> int launch_solve_fwd_generic(hipStream_t s, const SolveArgs<R> &a, int method);
-template <typename R> int launch_solve_bwd_generic(hipStream_t s, const AdjArgs<R> &a, int L, int method);
 template <typename R> int launch_rhs_fwd_generic(hipStream_t s, const RhsArgs<R> &a, int L);
+// adjoint and RHS backward (hode_generic_bwd.hip)
+template <typename R> int launch_solve_bwd_generic(hipStream_t s, const AdjArgs<R> &a, int L, int method);
 template <typename R> int launch_rhs_bwd_generic(hipStream_t s, const RhsArgs<R> &a, int L);
+// tb = 2 / 4 / 8 trajectories per eight-wave team (hode_generic_bwd_multi.hip; fp32, L - 1 <= 4, gradient rows: launch_solve_bwd_generic
+// decides when)
+int launch_solve_bwd_generic_multi(hipStream_t s, const AdjArgs<float> &a, int L, int method, int tb);
 // the same with input gradients (hode_generic_gin.hip; launch_*_generic route requests there): one-trajectory teams for every batch
 template <typename R> int launch_solve_bwd_generic_gin(hipStream_t s, const AdjInArgs<R> &a, int L, int method);
 template <typename R> int launch_rhs_bwd_generic_gin(hipStream_t s, const RhsArgs<R> &a, int L);
@@ -315,7 +325,7 @@ inline size_t tape_total_bytes(int B, int max_steps, size_t elem, int H, int L)
 {
     const size_t o = tape_partials_offset(B, max_steps, elem, H, L);
     // (generic shapes: the fp32 team kernels write gradient rows as well since round 4; fp64 and networks with more than four hidden
-    //  matrices keep the coalesced atomics of hode_generic.hip)
+    //  matrices keep the coalesced atomics of hode_generic_vjp.h)
     if (!tuned_shape(H, L) && elem != 4) return o;
     return o + (size_t)adj_partial_rows(B) * adj_partial_rowlen(nn_param_count(H, L)) * elem;
 }

@@ -1,7 +1,7 @@
 // hode_rhs_eval.h -- the right-hand side f(t, x, u) = mechanistic part + residual network of ONE evaluation by one wave: the 17
 // ODE constants, the state broadcasts, mech_eval, rhs_eval, and the shader-clock stamps of the HODE_FWD_TRACE experiment build.
 // Used by: hode_solve_body.h (every forward solve), hode_rhs.hip, hode_solve_jvp.hip, hode_adjoint.h (OdeP; the adjoints re-evaluate
-// nothing), hode_generic.hip.
+// nothing), hode_generic_rhs.h.
 #pragma once
 #include "hode_mlp.h"
 

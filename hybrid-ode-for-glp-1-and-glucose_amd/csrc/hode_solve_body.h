@@ -1,5 +1,6 @@
 // hode_solve_body.h -- the integration of ONE trajectory by ONE wavefront, shared by the two forward kernels
-// (register-resident weights: hode_solve_fwd.hip; hidden matrices in a workgroup-shared LDS image: lab/hode_solve_fwd_wg.hip).
+// (register-resident weights: hode_solve_fwd.hip; hidden matrices in a workgroup-shared LDS image: lab/hode_solve_fwd_wg.hip)
+// and by the generic path (hode_generic_rhs.h, hode_generic.hip).
 //
 // Replaces the body of the per-patient loop of HybridODENN.forward (reference models/hybrid_ode_nn.py:184-256): the
 // scipy.integrate.solve_ivp call, the RHS round trip through NumPy and the input interpolation (:210-231).
@@ -46,7 +47,7 @@ template <> struct Eps<double> { static constexpr double v = 2.220446049250313e-
 // The right-hand side as a functor: F = rhs(t, Y, meal, tvns, gde, rec) evaluates f(t, x, u) in the replicated state
 // layout and, when rec != nullptr, records what the adjoint needs for this stage (layer activations + stage state) at rec.
 //   RhsRegs  : the tuned path -- every weight in registers (MlpRegs) or, in the lab library, hidden matrices in an LDS image (MlpLds)
-//   RhsStream: the generic path (hode_generic.h) -- H <= 128, any depth, weights streamed from L2
+//   RhsStream: the generic path (hode_generic_rhs.h) -- H <= 128, any depth, weights streamed from L2
 template <typename R, int NL, typename WT> struct RhsRegs {
     const WT &W;
     const OdeP<R> &o;

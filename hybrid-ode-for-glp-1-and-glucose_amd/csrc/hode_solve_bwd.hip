@@ -60,10 +60,7 @@ template <typename R, int NL> __host__ __device__ constexpr size_t bwd_lds_elems
 // WTREG = true (fp32): 4 waves per workgroup, transposed matrices in registers, 1 wave/SIMD, no LDS wait
 //         inside the 64-FMA loops.
 // GIN: also the gradients of the external inputs (a.gmeal / a.gtvns / a.ggd), see gin_flush below.
-// (the GIN instantiations take AdjInArgs: the argument block of the others stays AdjArgs)
-template <typename R> __device__ __forceinline__ R *gin_row(const AdjArgs<R> &, int) { return nullptr; }
-template <typename R> __device__ __forceinline__ R *gin_row(const AdjInArgs<R> &a, int q) { return (q == 0) ? a.gmeal : (q == 1) ? a.gtvns : a.ggd; }
-template <typename R, bool GIN> using AdjArgsT = std::conditional_t<GIN, AdjInArgs<R>, AdjArgs<R>>;
+// (the GIN instantiations take AdjInArgs: the argument block of the others stays AdjArgs -- AdjArgsT, hode_kernels.h)
 template <typename R, int NL, bool GODE, bool WTREG, bool GD, bool GIN>
 __global__ __launch_bounds__(WTREG ? 256 : 64 * kBwdWaves, (sizeof(R) == 4 && !WTREG ? 2 : 1)) void solve_bwd_kernel(const AdjArgsT<R, GIN> a, const int method)
 {

@@ -1,6 +1,6 @@
 // hode_tableau.h -- the Runge-Kutta tableaux as device data and the two LDS coefficient-row stores.
-// Used by: hode_solve_body.h (the forward solves), hode_solve_jvp.hip, hode_solve_bwd.hip, hode_solve_bwd_ws.hip, hode_generic.hip,
-// lab/hode_solve_bwd_split.hip.
+// Used by: hode_solve_body.h (the forward solves), hode_solve_jvp.hip, hode_solve_bwd.hip, hode_solve_bwd_ws.hip, hode_generic_vjp.h,
+// hode_generic_bwd_multi.hip, lab/hode_solve_bwd_split.hip.
 #pragma once
 #include "hode_xlane.h"
 #include "../../include/hode.h"

@@ -1,7 +1,7 @@
 // hode_xlane.h -- wave-level primitives of every kernel (gfx950 / CDNA4 only): bit casts, lane broadcasts, DPP moves, the cross-lane
 // sums, the rotating-operand FMA, the per-dtype math wrappers (r*) and atomic_add.
-// Used by: every other device header (hode_tableau.h, hode_mlp.h, hode_rhs_eval.h, hode_adjoint.h, lab/hode_lab_layers.h),
-// hode_optim.hip, and hode_rhs.hip's self test.
+// Used by: every other device header (hode_tableau.h, hode_mlp.h, hode_rhs_eval.h, hode_adjoint.h, hode_generic_net.h,
+// lab/hode_lab_layers.h), hode_optim.hip, and hode_rhs.hip's self test.
 //
 // Execution model used throughout: ONE TRAJECTORY PER WAVEFRONT, ONE HIDDEN UNIT PER LANE.
 //   * the hidden weight matrices live in VGPRs, 64 registers per matrix and lane (loaded once per trajectory, register-

@@ -509,8 +509,12 @@ def test_translation_units_include_only_their_concern():
     with ThreadPoolExecutor(4) as pool:
         deps = dict(zip(srcs, pool.map(_deps, srcs)))
     assert "hode_rhs_eval.h" in deps["hode_solve_fwd.hip"] and "hode_adjoint.h" in deps["hode_solve_bwd.hip"]      # the parse sees headers
-    for fwd in ("hode_solve_fwd.hip", "hode_rhs.hip"):
+    for fwd in ("hode_solve_fwd.hip", "hode_rhs.hip", "hode_generic.hip"):
         assert "hode_adjoint.h" not in deps[fwd], fwd
+    # no source is made by including another one: the input-gradient unit of the generic path is a source like the others
+    assert "hode_generic_vjp.h" in deps["hode_generic_gin.hip"]
+    for src, d in deps.items():
+        assert not [f for f in d if f.endswith(".hip") and f != src], (src, d)
     top, _ = _csrc_headers()
     device_headers = {os.path.basename(h) for h in top} - {"hode_kernels.h"}
     assert not (deps["hode_capi.hip"] & device_headers), deps["hode_capi.hip"] & device_headers

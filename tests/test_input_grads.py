@@ -47,6 +47,8 @@ def test_gradient_of_an_absent_input_is_rejected_before_any_launch():
 
 def test_no_dpp_or_lds_hazard_in_the_adjoint_sources():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "dpp_hazard_check.py"), os.path.join(CSRC, "hode_solve_bwd.hip"),
-                        os.path.join(CSRC, "hode_generic.hip"), os.path.join(CSRC, "hode_generic_gin.hip")],
+                        os.path.join(CSRC, "hode_generic_bwd.hip"), os.path.join(CSRC, "hode_generic_bwd_multi.hip"),
+                        os.path.join(CSRC, "hode_generic_gin.hip"), os.path.join(CSRC, "hode_generic.hip")],     # (the last: the forward
+                       # kernels of the generic path, which this check has covered since they shared a file with its adjoint)
                        capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0 and "0 hazard(s)" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

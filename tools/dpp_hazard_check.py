@@ -20,7 +20,8 @@ import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hybrid-ode-for-glp-1-and-glucose_amd", "csrc")
 srcs = [a for a in sys.argv[1:] if not a.startswith("-")] or [os.path.join(CSRC, f) for f in
-        ("hode_solve_fwd.hip", "hode_solve_bwd_ws.hip", "hode_solve_bwd.hip", "hode_rhs.hip", "hode_generic.hip")]
+        ("hode_solve_fwd.hip", "hode_solve_bwd_ws.hip", "hode_solve_bwd.hip", "hode_rhs.hip", "hode_generic.hip", "hode_generic_bwd.hip",
+         "hode_generic_bwd_multi.hip")]
 flags = [a for a in sys.argv[1:] if a.startswith("-")]
 
 
