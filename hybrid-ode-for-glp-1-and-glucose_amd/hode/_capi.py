@@ -5,9 +5,12 @@ import os
 
 import torch
 
+from ._abi import SYMBOLS, HodeError, bind  # noqa: F401
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("HODE_LIB") or os.path.join(_HERE, "libhode.so")   # HODE_LIB: development builds
 _lib = None
+_fns = {}                                     # (family, dtype or None) -> the declared ctypes function
 
 METHOD_DP54 = 0
 METHOD_RK4 = 1
@@ -16,32 +19,7 @@ ST_OK, ST_MAXSTEPS, ST_UNDERFLOW, ST_NONFINITE = 0, 1, 2, 3
 _ERR = {-1: "HODE_EINVAL (bad argument)", -2: "HODE_EUNSUPPORTED (shape outside the supported range: H<=128, L<=8, activation code <= 3)",
         -3: "HODE_ELAUNCH (HIP launch failed)"}
 
-# every symbol include/hode.h declares (tests check that the library exports all of them)
-SYMBOLS = ["hode_version", "hode_nn_param_count", "hode_tape_bytes", "hode_tape_bytes_hl", "hode_rhs_fwd_f32", "hode_rhs_fwd_f64",
-           "hode_rhs_bwd_f32", "hode_rhs_bwd_f64", "hode_solve_fwd_f32", "hode_solve_fwd_f64",
-           "hode_solve_bwd_f32", "hode_solve_bwd_f64", "hode_adam_step_f32", "hode_mse_fwd_bwd_f32",
-           "hode_selftest_xlane", "hode_4gi_default_params", "hode_4gi_generate_f64", "hode_4gi_rhs_f64",
-           "hode_4gi_windows_f32", "hode_4gi_window_moments_f64",
-           "hode_solve_bwd_inputs_f32", "hode_solve_bwd_inputs_f64", "hode_rhs_bwd_inputs_f32", "hode_rhs_bwd_inputs_f64",
-           "hode_mse_sets_f32", "hode_mse_sets_f64", "hode_hmc_refresh_f32", "hode_hmc_refresh_f64", "hode_hmc_leapfrog_f32",
-           "hode_hmc_leapfrog_f64", "hode_hmc_accept_f32", "hode_hmc_accept_f64", "hode_hmc_welford_f32", "hode_hmc_welford_f64",
-           "hode_solve_jvp_f32", "hode_solve_jvp_f64", "hode_solve_jvp_any_f32", "hode_solve_jvp_any_f64",
-           "hode_nuts_begin_f32", "hode_nuts_begin_f64", "hode_nuts_pre_f32", "hode_nuts_pre_f64", "hode_nuts_post_f32",
-           "hode_nuts_post_f64", "hode_nuts_compact", "hode_nuts_finish_f32", "hode_nuts_finish_f64",
-           "hode_obs_nll_sets_f32", "hode_obs_nll_sets_f64", "hode_sobol_indices_f32", "hode_sobol_indices_f64",
-           "hode_pred_fold_f32", "hode_pred_fold_f64", "hode_pred_score_f32", "hode_pred_score_f64",
-           "hode_pred_tails_f32", "hode_pred_tails_f64", "hode_pred_quantiles_f32", "hode_pred_quantiles_f64",
-           "hode_pred_loo_fold_f32", "hode_pred_loo_fold_f64", "hode_pred_loo_finish_f32", "hode_pred_loo_finish_f64",
-           "hode_pop_params_f32", "hode_pop_params_f64", "hode_pop_grad_f32", "hode_pop_grad_f64",
-           "hode_x0_params_f32", "hode_x0_params_f64", "hode_x0_grad_f32", "hode_x0_grad_f64",
-           "hode_pf_step_f32", "hode_pf_step_f64", "hode_pf_smooth_f32", "hode_pf_smooth_f64",
-           "hode_pf_params_f32", "hode_pf_params_f64", "hode_ukf_step_f32", "hode_ukf_step_f64"]
-
 INPUT_KEYS = ("meal", "tVNS", "GD")
-
-
-class HodeError(RuntimeError):
-    pass
 
 
 def lib_path():
@@ -69,12 +47,9 @@ def load():
             if want is not None and os.path.abspath(_SO) == os.path.abspath(_build.LAB_SO) and _build.binary_stamp(_SO) != want:
                 raise HodeError(f"{_SO} is stale (binary {_build.binary_stamp(_SO)}, sources {want}): `make -C {_build.CSRC} lab`; "
                                 "HODE_ALLOW_STALE=1 loads it anyway")
-        _lib = C.CDLL(_SO)
-        _lib.hode_version.restype = C.c_char_p
-        _lib.hode_tape_bytes.restype = C.c_size_t
-        _lib.hode_tape_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-        _lib.hode_tape_bytes_hl.restype = C.c_size_t
-        _lib.hode_tape_bytes_hl.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib = C.CDLL(_SO)
+        _fns.update(bind(lib, _SO))            # restype and argtypes of every symbol of include/hode.h
+        _lib = lib
     return _lib
 
 
@@ -107,19 +82,35 @@ def _need_gpu(t):
 
 
 def _ptr(t):
+    """For raw calls of a library function by hand (tests do): the wrappers below pass tensors as they are."""
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
-def _sfx(dtype):
-    if dtype == torch.float32:
-        return "f32"
-    if dtype == torch.float64:
-        return "f64"
-    raise HodeError(f"unsupported dtype {dtype}")
+def _call(name, dtype, *args):
+    """Enqueue hode_<name>_f32 / _f64 (by dtype; None: the one symbol hode_<name>) on torch's current stream.  Arguments are plain
+    values -- ints, floats, tensors, None, host arrays -- marshalled and dtype-checked by the argtypes of hode/_abi.py."""
+    try:
+        fn = _fns[name, dtype]
+    except KeyError:                            # the library is not loaded yet, or there is no such instantiation
+        if _lib is not None:
+            raise HodeError(f"unsupported dtype {dtype}") from None
+        load()
+        return _call(name, dtype, *args)
+    try:
+        rc = fn(_stream(), *args)
+    except C.ArgumentError as e:                # ctypes relabels what a parameter's from_param raised: give it its type back
+        raise (HodeError if "HodeError" in str(e) else TypeError)(f"hode_{name}: {e}") from None
+    if rc != 0:
+        _check(rc, f"hode_{name}")
+
+
+def _need_real(dtype):
+    if dtype not in (torch.float32, torch.float64):
+        raise HodeError(f"unsupported dtype {dtype}")
 
 
 def _prep(t, dtype, dev):
@@ -141,7 +132,7 @@ def _mode(t, B, T):
 
 def selftest_xlane(device="cuda"):
     out = torch.zeros(64 * 12, dtype=torch.int32, device=device)
-    _check(load().hode_selftest_xlane(_stream(), _ptr(out)), "hode_selftest_xlane")
+    _call("selftest_xlane", None, out)
     return out.view(64, 12)
 
 
@@ -154,9 +145,7 @@ def rhs_fwd(x, t, meal, tvns, gd, ode_p, nn_p, H, L):
     ode_p, nn_p = _prep(ode_p, dt, dev), _prep(nn_p, dt, dev)
     assert nn_p.numel() == n_params(H, L) and ode_p.numel() == 17
     out = torch.empty(B, 6, dtype=dt, device=dev)
-    fn = getattr(load(), f"hode_rhs_fwd_{_sfx(dt)}")
-    _check(fn(_stream(), C.c_int(B), _ptr(x), _ptr(t), _ptr(meal), _ptr(tvns), _ptr(gd), _ptr(ode_p), _ptr(nn_p),
-              C.c_int(H), C.c_int(L), _ptr(out)), "hode_rhs_fwd")
+    _call("rhs_fwd", dt, B, x, t, meal, tvns, gd, ode_p, nn_p, H, L, out)
     return out
 
 
@@ -214,14 +203,8 @@ def solve_fwd(x0, t, meal, tvns, gd, ode_p, nn_p, H, L, method=METHOD_DP54, rtol
             s.tape = tape
         else:
             s.tape = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    fn = getattr(load(), f"hode_solve_fwd_{_sfx(dt)}")
-    rc = fn(_stream(), C.c_int(B), C.c_int(T), _ptr(x0), _ptr(t), C.c_int(t_batched),
-            _ptr(meal), C.c_int(_mode(meal, B, T)), _ptr(tvns), C.c_int(_mode(tvns, B, T)),
-            _ptr(gd), C.c_int(_mode(gd, B, T)), _ptr(ode_p), _ptr(nn_p), C.c_int(n_sets), C.c_int(H),
-            C.c_int(L | (NN_SHARED if nn_shared else 0)),
-            C.c_int(method), C.c_double(rtol), C.c_double(atol), C.c_int(max_steps), _ptr(s.y), _ptr(s.status),
-            _ptr(s.nsteps), _ptr(s.nfev), _ptr(s.tape))
-    _check(rc, "hode_solve_fwd")
+    _call("solve_fwd", dt, B, T, x0, t, t_batched, meal, _mode(meal, B, T), tvns, _mode(tvns, B, T), gd, _mode(gd, B, T), ode_p, nn_p,
+          n_sets, H, L | (NN_SHARED if nn_shared else 0), method, rtol, atol, max_steps, s.y, s.status, s.nsteps, s.nfev, s.tape)
     s.ctx = (t, t_batched, meal, tvns, gd, ode_p, nn_p, n_sets, H, L, method)
     return s
 
@@ -251,19 +234,22 @@ def _solve_bwd(sol, gy, want_gnn, want_gode, want_inputs):
     gx0 = torch.empty(B, 6, dtype=dt, device=dev)
     gnn = torch.zeros(nn_p.numel(), dtype=dt, device=dev) if want_gnn else None
     gode = torch.zeros(17 * n_sets, dtype=dt, device=dev) if want_gode else None
-    args = [_stream(), C.c_int(B), C.c_int(T), _ptr(t), C.c_int(t_batched),
-            _ptr(meal), C.c_int(_mode(meal, B, T)), _ptr(tvns), C.c_int(_mode(tvns, B, T)),
-            _ptr(gd), C.c_int(_mode(gd, B, T)), _ptr(ode_p), _ptr(nn_p), C.c_int(n_sets), C.c_int(H), C.c_int(L),
-            C.c_int(method), C.c_int(sol.max_steps), _ptr(sol.nsteps), _ptr(sol.status), _ptr(sol.tape), _ptr(gy),
-            _ptr(gx0), _ptr(gnn), _ptr(gode)]
+    args = _taped_args(sol) + (sol.tape, gy, gx0, gnn, gode)
     if want_inputs is None:
-        _check(getattr(load(), f"hode_solve_bwd_{_sfx(dt)}")(*args), "hode_solve_bwd")
+        _call("solve_bwd", dt, *args)
         return gx0, gnn, gode, None
     gin = {k: (torch.empty_like(u) if (u is not None and k in want_inputs) else None)
            for k, u in zip(INPUT_KEYS, (meal, tvns, gd))}
-    _check(getattr(load(), f"hode_solve_bwd_inputs_{_sfx(dt)}")(*args, *(_ptr(gin[k]) for k in INPUT_KEYS)),
-           "hode_solve_bwd_inputs")
+    _call("solve_bwd_inputs", dt, *args, *(gin[k] for k in INPUT_KEYS))
     return gx0, gnn, gode, gin
+
+
+def _taped_args(sol):
+    """The arguments that hode_solve_bwd_*, hode_solve_bwd_inputs_* and hode_solve_jvp*_ share: the solve, up to its tape."""
+    t, t_batched, meal, tvns, gd, ode_p, nn_p, n_sets, H, L, method = sol.ctx
+    B, T = sol.y.shape[:2]
+    return (B, T, t, t_batched, meal, _mode(meal, B, T), tvns, _mode(tvns, B, T), gd, _mode(gd, B, T), ode_p, nn_p, n_sets, H, L,
+            method, sol.max_steps, sol.nsteps, sol.status)
 
 
 def solve_jvp(sol, v_ode=None, v_x0=None):
@@ -288,12 +274,7 @@ def solve_jvp(sol, v_ode=None, v_x0=None):
     if v_x0 is not None and tuple(v_x0.shape) != (B, K, 6):
         raise HodeError(f"v_x0 must be [B,K,6]=({B},K,6), got {tuple(v_x0.shape)}")
     dy = torch.empty(B, K, T, 6, dtype=dt, device=dev)
-    fn = getattr(load(), f"hode_solve_jvp_any_{_sfx(dt)}")
-    _check(fn(_stream(), C.c_int(B), C.c_int(T), _ptr(t), C.c_int(t_batched),
-              _ptr(meal), C.c_int(_mode(meal, B, T)), _ptr(tvns), C.c_int(_mode(tvns, B, T)),
-              _ptr(gd), C.c_int(_mode(gd, B, T)), _ptr(ode_p), _ptr(nn_p), C.c_int(n_sets), C.c_int(H), C.c_int(L),
-              C.c_int(method), C.c_int(sol.max_steps), _ptr(sol.nsteps), _ptr(sol.status), _ptr(sol.tape), C.c_int(K),
-              _ptr(v_ode), _ptr(v_x0), _ptr(dy)), "hode_solve_jvp_any")
+    _call("solve_jvp_any", dt, *_taped_args(sol), sol.tape, K, v_ode, v_x0, dy)
     return dy
 
 
@@ -319,14 +300,13 @@ def _rhs_bwd(x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, want_gt, want_gnn, w
     gt = torch.empty(B, dtype=dt, device=dev) if want_gt else None
     gnn = torch.zeros(nn_p.numel(), dtype=dt, device=dev) if want_gnn else None
     gode = torch.zeros(17, dtype=dt, device=dev) if want_gode else None
-    args = [_stream(), C.c_int(B), _ptr(x), _ptr(t), _ptr(meal), _ptr(tvns), _ptr(gd), _ptr(ode_p), _ptr(nn_p),
-            C.c_int(H), C.c_int(L), _ptr(gout), _ptr(gx), _ptr(gt), _ptr(gnn), _ptr(gode)]
+    args = (B, x, t, meal, tvns, gd, ode_p, nn_p, H, L, gout, gx, gt, gnn, gode)
     if want_inputs is None:
-        _check(getattr(load(), f"hode_rhs_bwd_{_sfx(dt)}")(*args), "hode_rhs_bwd")
+        _call("rhs_bwd", dt, *args)
         return gx, gt, gnn, gode, None
     gin = {k: (torch.empty(B, dtype=dt, device=dev) if (u is not None and k in want_inputs) else None)
            for k, u in zip(INPUT_KEYS, (meal, tvns, gd))}
-    _check(getattr(load(), f"hode_rhs_bwd_inputs_{_sfx(dt)}")(*args, *(_ptr(gin[k]) for k in INPUT_KEYS)), "hode_rhs_bwd_inputs")
+    _call("rhs_bwd_inputs", dt, *args, *(gin[k] for k in INPUT_KEYS))
     return gx, gt, gnn, gode, gin
 
 
@@ -339,10 +319,7 @@ def adam_step(p, g, m, v, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=1, max_norm
             raise HodeError("adam_step needs contiguous fp32 tensors")
     if scratch is None:
         scratch = torch.empty(2, dtype=torch.float32, device=p.device)
-    _check(load().hode_adam_step_f32(_stream(), C.c_int64(p.numel()), _ptr(p), _ptr(g), _ptr(m), _ptr(v),
-                                     C.c_float(lr), C.c_float(beta1), C.c_float(beta2), C.c_float(eps), C.c_int(step),
-                                     C.c_float(max_norm), C.c_float(grad_scale), C.c_float(weight_decay),
-                                     _ptr(scratch)), "hode_adam_step")
+    _call("adam_step_f32", None, p.numel(), p, g, m, v, lr, beta1, beta2, eps, step, max_norm, grad_scale, weight_decay, scratch)
     return scratch
 
 
@@ -356,8 +333,7 @@ def mse_fwd_bwd(y, obs, scale, loss_sum=None, want_grad=True):
     if loss_sum is None:
         loss_sum = torch.zeros(1, dtype=torch.float64, device=y.device)
     gy = torch.empty_like(y) if want_grad else None
-    _check(load().hode_mse_fwd_bwd_f32(_stream(), C.c_int64(y.numel()), _ptr(y), _ptr(obs), C.c_float(scale),
-                                       _ptr(loss_sum), _ptr(gy)), "hode_mse_fwd_bwd")
+    _call("mse_fwd_bwd_f32", None, y.numel(), y, obs, scale, loss_sum, gy)
     return loss_sum, gy
 
 
@@ -365,10 +341,6 @@ def mse_fwd_bwd(y, obs, scale, loss_sum=None, want_grad=True):
 HMC_ASSEMBLE, HMC_KICK, HMC_DRIFT, HMC_KE, HMC_PARAMS = 1, 2, 4, 8, 16
 HMC_SAMPLE, HMC_ADAPT, HMC_SEARCH, HMC_DA_RESTART, HMC_DA_FINISH = 0, 1, 2, 3, 4
 HMC_WELFORD_ACCUM, HMC_WELFORD_FINISH = 1, 2
-
-
-def _real(dt):
-    return C.c_float if dt == torch.float32 else C.c_double
 
 
 def mse_sets(y, obs, scale, loss_sum, want_grad=True):
@@ -381,8 +353,7 @@ def mse_sets(y, obs, scale, loss_sum, want_grad=True):
     if y.numel() != n_sets * obs.numel() or loss_sum.dtype != torch.float64 or loss_sum.numel() < n_sets:
         raise HodeError("mse_sets: y must be [n_sets, len(obs)] and loss_sum fp64[n_sets]")
     gy = torch.empty_like(y) if want_grad else None
-    _check(getattr(load(), f"hode_mse_sets_{_sfx(y.dtype)}")(_stream(), C.c_int(n_sets), C.c_int64(obs.numel()), _ptr(y), _ptr(obs),
-                                                           _real(y.dtype)(scale), _ptr(loss_sum), _ptr(gy)), "hode_mse_sets")
+    _call("mse_sets", y.dtype, n_sets, obs.numel(), y, obs, scale, loss_sum, gy)
     return gy
 
 
@@ -412,9 +383,7 @@ def obs_nll_sets(y, obs, mask, mode, sse, loss_sum=None, w=None, a=None, b=None,
         if mask.dtype != torch.uint8 or mask.numel() != obs.numel():
             raise HodeError("obs_nll_sets: mask must be uint8 with the shape of obs")
     gy = torch.empty_like(y) if want_grad and flags != OBS_SUMS_ONLY else None
-    _check(getattr(load(), f"hode_obs_nll_sets_{_sfx(y.dtype)}")(_stream(), C.c_int(n_sets), C.c_int64(obs.numel()), _ptr(y), _ptr(obs),
-                                                               _ptr(mask), C.c_int(mode), C.c_int(flags), _six(w), _six(a), _six(b),
-                                                               _six(n), _ptr(sse), _ptr(loss_sum), _ptr(gy)), "hode_obs_nll_sets")
+    _call("obs_nll_sets", y.dtype, n_sets, obs.numel(), y, obs, mask, mode, flags, _six(w), _six(a), _six(b), _six(n), sse, loss_sum, gy)
     return gy
 
 
@@ -443,16 +412,41 @@ def sobol_indices(Y, D, second_order=True, R=100, seed=0, conf_z=1.9599639845400
     new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)                     # noqa: E731
     out = {"S1": new(M, D), "ST": new(M, D), "S2": new(M, D, D) if second_order else None,
            "S1_conf": new(M, D), "ST_conf": new(M, D), "S2_conf": new(M, D, D) if second_order else None, "variance": new(M)}
-    _check(getattr(load(), f"hode_sobol_indices_{_sfx(Y.dtype)}")(
-        _stream(), C.c_int(rows // nb), C.c_int(D), C.c_int(M), _ptr(Y), C.c_int64(Y.stride(0)), C.c_int(int(bool(second_order))),
-        C.c_int(int(R)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_double(conf_z), _ptr(out["S1"]), _ptr(out["ST"]), _ptr(out["S2"]),
-        _ptr(out["S1_conf"]), _ptr(out["ST_conf"]), _ptr(out["S2_conf"]), _ptr(out["variance"])), "hode_sobol_indices")
+    _call("sobol_indices", Y.dtype, rows // nb, D, M, Y, Y.stride(0), int(bool(second_order)), int(R), int(seed), conf_z,
+          out["S1"], out["ST"], out["S2"], out["S1_conf"], out["ST_conf"], out["S2_conf"], out["variance"])
     return out
 
 
 PF_MAX_PARTICLES, PF_MAX_AUX, PF_COLS = 4096, 17, 16
 PF_LINK = {"additive": 0, "log": 1}
 PF_STATS = ("log_evidence", "ess", "resampled", "alive")          # stats columns 0..3; 4..9 the means, 10..15 the variances
+
+
+def _need_vectors(what, dev, dtype, named):
+    for name, v, n in named:
+        if v.dtype != dtype or v.device != dev or v.numel() != n or not v.is_contiguous():
+            raise HodeError(f"{what}: {name} must be a contiguous {'fp64' if dtype == torch.float64 else 'int32'} device tensor of "
+                            f"{n} elements")
+
+
+def _obs_mask_status(what, obs, mask, status, B, n, n_name, dev, dtype):
+    obs = obs.to(device=dev, dtype=dtype).contiguous()
+    if obs.numel() != 6 * B:
+        raise HodeError(f"{what}: obs must be [B, 6]")
+    if mask is not None:
+        mask = mask.to(device=dev).contiguous()
+        if mask.dtype != torch.uint8 or mask.numel() != 6 * B:
+            raise HodeError(f"{what}: mask must be uint8 [B, 6]")
+    if status is not None:
+        status = status.to(device=dev).contiguous()
+        if status.dtype != torch.int32 or status.numel() != B * n:
+            raise HodeError(f"{what}: status must be int32 [B, {n_name}]")
+    return obs, mask, status
+
+
+def _is_buffer(t, dtype, dev, shape=None, numel=None):
+    return (t.dtype == dtype and t.device == dev and t.is_contiguous()
+            and (tuple(t.shape) == tuple(shape) if numel is None else t.numel() == numel))
 
 
 def pf_step(x_in, obs, sigma, q, dt, lw, step, seed=0, id0=0, link=1, ess_frac=0.5, status=None, mask=None, aux_in=None, out=None):
@@ -468,20 +462,8 @@ def pf_step(x_in, obs, sigma, q, dt, lw, step, seed=0, id0=0, link=1, ess_frac=0
     dev, dt_ = x_in.device, x_in.dtype
     if N > PF_MAX_PARTICLES:
         raise HodeError(f"pf_step: N = {N} particles, the kernel takes up to {PF_MAX_PARTICLES} (HODE_PF_MAX_PARTICLES)")
-    obs = obs.to(device=dev, dtype=dt_).contiguous()
-    if obs.numel() != 6 * B:
-        raise HodeError("pf_step: obs must be [B, 6]")
-    for name, v, n in (("sigma", sigma, 6), ("q", q, 6), ("dt", dt, B), ("lw", lw, B * N)):
-        if v.dtype != torch.float64 or v.device != dev or v.numel() != n or not v.is_contiguous():
-            raise HodeError(f"pf_step: {name} must be a contiguous fp64 device tensor of {n} elements")
-    if mask is not None:
-        mask = mask.to(device=dev).contiguous()
-        if mask.dtype != torch.uint8 or mask.numel() != 6 * B:
-            raise HodeError("pf_step: mask must be uint8 [B, 6]")
-    if status is not None:
-        status = status.to(device=dev).contiguous()
-        if status.dtype != torch.int32 or status.numel() != B * N:
-            raise HodeError("pf_step: status must be int32 [B, N]")
+    obs, mask, status = _obs_mask_status("pf_step", obs, mask, status, B, N, "N", dev, dt_)
+    _need_vectors("pf_step", dev, torch.float64, (("sigma", sigma, 6), ("q", q, 6), ("dt", dt, B), ("lw", lw, B * N)))
     n_aux = 0
     if aux_in is not None:
         if aux_in.dim() != 3 or tuple(aux_in.shape[:2]) != (B, N) or aux_in.dtype != dt_ or aux_in.device != dev or not aux_in.is_contiguous():
@@ -491,11 +473,8 @@ def pf_step(x_in, obs, sigma, q, dt, lw, step, seed=0, id0=0, link=1, ess_frac=0
         out = (torch.empty_like(x_in), torch.empty(B, N, dtype=torch.int32, device=dev),
                torch.empty(B, PF_COLS, dtype=torch.float64, device=dev), None if aux_in is None else torch.empty_like(aux_in))
     x_out, anc, stats, aux_out = out
-    _check(getattr(load(), f"hode_pf_step_{_sfx(dt_)}")(
-        _stream(), C.c_int(B), C.c_int(N), C.c_uint32(int(step) & 0xFFFFFFFF), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-        C.c_uint32(int(id0) & 0xFFFFFFFF), _ptr(x_in), _ptr(status), _ptr(obs), _ptr(mask), _ptr(sigma), _ptr(q), _ptr(dt),
-        C.c_int(int(link)), C.c_double(float(ess_frac)), _ptr(lw), _ptr(x_out), _ptr(anc), _ptr(stats), C.c_int(n_aux), _ptr(aux_in),
-        _ptr(aux_out)), "hode_pf_step")
+    _call("pf_step", dt_, B, N, int(step), int(seed), int(id0), x_in, status, obs, mask, sigma, q, dt, int(link), float(ess_frac), lw,
+          x_out, anc, stats, n_aux, aux_in, aux_out)
     return x_out, anc, stats, aux_out
 
 
@@ -516,19 +495,13 @@ def pf_smooth(hist, lwh, pred, q, dt, M, seed=0, id0=0, link=1, out=None):
         raise HodeError(f"pf_smooth: N = {N} particles, the kernel takes up to {PF_MAX_PARTICLES} (HODE_PF_MAX_PARTICLES)")
     if pred.shape != hist.shape or pred.dtype != dt_ or pred.device != dev or not pred.is_contiguous():
         raise HodeError("pf_smooth: pred must be a contiguous [S, B, N, 6] of hist's dtype")
-    for name, v, n in (("lwh", lwh, S * B * N), ("q", q, 6), ("dt", dt, S * B)):
-        if v.dtype != torch.float64 or v.device != dev or v.numel() != n or not v.is_contiguous():
-            raise HodeError(f"pf_smooth: {name} must be a contiguous fp64 device tensor of {n} elements")
+    _need_vectors("pf_smooth", dev, torch.float64, (("lwh", lwh, S * B * N), ("q", q, 6), ("dt", dt, S * B)))
     if out is None:
         out = (torch.empty(S, B, M, dtype=torch.int32, device=dev), torch.empty(S, B, M, 6, dtype=dt_, device=dev))
     idx, paths = out
-    if (idx.dtype != torch.int32 or tuple(idx.shape) != (S, B, M) or idx.device != dev or not idx.is_contiguous()
-            or paths.dtype != dt_ or tuple(paths.shape) != (S, B, M, 6) or paths.device != dev or not paths.is_contiguous()):
+    if not (_is_buffer(idx, torch.int32, dev, (S, B, M)) and _is_buffer(paths, dt_, dev, (S, B, M, 6))):
         raise HodeError("pf_smooth: out must be (idx int32 [S, B, M], paths [S, B, M, 6] of hist's dtype), contiguous")
-    _check(getattr(load(), f"hode_pf_smooth_{_sfx(dt_)}")(
-        _stream(), C.c_int(B), C.c_int(N), C.c_int(M), C.c_int(S), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-        C.c_uint32(int(id0) & 0xFFFFFFFF), _ptr(hist), _ptr(lwh), _ptr(pred), _ptr(q), _ptr(dt), C.c_int(int(link)), _ptr(idx),
-        _ptr(paths)), "hode_pf_smooth")
+    _call("pf_smooth", dt_, B, N, M, S, int(seed), int(id0), hist, lwh, pred, q, dt, int(link), idx, paths)
     return idx, paths
 
 
@@ -548,22 +521,16 @@ def pf_params(lw, aux, mode, walk, dt, step, shrink, seed=0, id0=0, out=None):
     dev = aux.device
     if N > PF_MAX_PARTICLES:
         raise HodeError(f"pf_params: N = {N} particles, the kernel takes up to {PF_MAX_PARTICLES} (HODE_PF_MAX_PARTICLES)")
-    for name, v, n in (("lw", lw, B * N), ("walk", walk, n_aux), ("dt", dt, B)):
-        if v.dtype != torch.float64 or v.device != dev or v.numel() != n or not v.is_contiguous():
-            raise HodeError(f"pf_params: {name} must be a contiguous fp64 device tensor of {n} elements")
-    if mode.dtype != torch.int32 or mode.device != dev or mode.numel() != n_aux or not mode.is_contiguous():
-        raise HodeError(f"pf_params: mode must be a contiguous int32 device tensor of {n_aux} elements")
+    _need_vectors("pf_params", dev, torch.float64, (("lw", lw, B * N), ("walk", walk, n_aux), ("dt", dt, B)))
+    _need_vectors("pf_params", dev, torch.int32, (("mode", mode, n_aux),))
     shrink = float(shrink)
     if not 0.0 <= shrink <= 1.0:
         raise HodeError("pf_params: shrink must lie in [0, 1]")
     if out is None:
         out = torch.empty(B, 2 * n_aux, dtype=torch.float64, device=dev)
-    if out.dtype != torch.float64 or out.device != dev or out.numel() != 2 * B * n_aux or not out.is_contiguous():
+    if not _is_buffer(out, torch.float64, dev, numel=2 * B * n_aux):
         raise HodeError("pf_params: out must be a contiguous fp64 [B, 2 * n_aux] on aux's device")
-    _check(getattr(load(), f"hode_pf_params_{_sfx(aux.dtype)}")(
-        _stream(), C.c_int(B), C.c_int(N), C.c_uint32(int(step) & 0xFFFFFFFF), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-        C.c_uint32(int(id0) & 0xFFFFFFFF), _ptr(lw), C.c_int(n_aux), _ptr(aux), _ptr(mode), _ptr(walk), _ptr(dt), C.c_double(shrink),
-        _ptr(out)), "hode_pf_params")
+    _call("pf_params", aux.dtype, B, N, int(step), int(seed), int(id0), lw, n_aux, aux, mode, walk, dt, shrink, out)
     return out
 
 
@@ -604,37 +571,21 @@ def ukf_step(x_in, aux_in, mode, obs, sigma, q, walk, dt, alive, mean, cov, weig
     dev, dt_ = x_in.device, x_in.dtype
     if tuple(aux_in.shape) != (B, K, PF_MAX_AUX) or aux_in.dtype != dt_ or aux_in.device != dev or not aux_in.is_contiguous():
         raise HodeError(f"ukf_step: aux_in must be a contiguous [B, K, {PF_MAX_AUX}] of x_in's dtype")
-    obs = obs.to(device=dev, dtype=dt_).contiguous()
-    if obs.numel() != 6 * B:
-        raise HodeError("ukf_step: obs must be [B, 6]")
-    for name, v, m in (("sigma", sigma, 6), ("q", q, 6), ("walk", walk, PF_MAX_AUX), ("dt", dt, B), ("mean", mean, B * n),
-                       ("cov", cov, B * n * n)):
-        if v.dtype != torch.float64 or v.device != dev or v.numel() != m or not v.is_contiguous():
-            raise HodeError(f"ukf_step: {name} must be a contiguous fp64 device tensor of {m} elements")
-    if alive.dtype != torch.int32 or alive.device != dev or alive.numel() != B or not alive.is_contiguous():
-        raise HodeError(f"ukf_step: alive must be a contiguous int32 device tensor of {B} elements")
-    if mask is not None:
-        mask = mask.to(device=dev).contiguous()
-        if mask.dtype != torch.uint8 or mask.numel() != 6 * B:
-            raise HodeError("ukf_step: mask must be uint8 [B, 6]")
-    if status is not None:
-        status = status.to(device=dev).contiguous()
-        if status.dtype != torch.int32 or status.numel() != B * K:
-            raise HodeError("ukf_step: status must be int32 [B, K]")
+    obs, mask, status = _obs_mask_status("ukf_step", obs, mask, status, B, K, "K", dev, dt_)
+    _need_vectors("ukf_step", dev, torch.float64, (("sigma", sigma, 6), ("q", q, 6), ("walk", walk, PF_MAX_AUX), ("dt", dt, B),
+                                                   ("mean", mean, B * n), ("cov", cov, B * n * n)))
+    _need_vectors("ukf_step", dev, torch.int32, (("alive", alive, B),))
     gamma, wm0, wc0, wi = (float(v) for v in weights)
     if out is None:
         out = (torch.empty_like(x_in), torch.empty_like(aux_in), torch.empty(B, UKF_COLS, dtype=torch.float64, device=dev))
     x_out, aux_out, stats = out
-    if (x_out.shape != x_in.shape or x_out.dtype != dt_ or x_out.device != dev or not x_out.is_contiguous()
-            or aux_out.shape != aux_in.shape or aux_out.dtype != dt_ or aux_out.device != dev or not aux_out.is_contiguous()
-            or stats.dtype != torch.float64 or stats.device != dev or stats.numel() != B * UKF_COLS or not stats.is_contiguous()):
+    if not (_is_buffer(x_out, dt_, dev, x_in.shape) and _is_buffer(aux_out, dt_, dev, aux_in.shape)
+            and _is_buffer(stats, torch.float64, dev, numel=B * UKF_COLS)):
         raise HodeError("ukf_step: out must be (x_out like x_in, aux_out like aux_in, stats fp64 [B, 16]), contiguous")
     if x_out.data_ptr() == x_in.data_ptr() or aux_out.data_ptr() == aux_in.data_ptr():
         raise HodeError("ukf_step: x_out may not alias x_in, aux_out may not alias aux_in")
-    _check(getattr(load(), f"hode_ukf_step_{_sfx(dt_)}")(
-        _stream(), C.c_int(B), C.c_int(1 if predict else 0), C.c_int(int(link)), (C.c_int32 * PF_MAX_AUX)(*mode), C.c_double(gamma),
-        C.c_double(wm0), C.c_double(wc0), C.c_double(wi), _ptr(x_in), _ptr(status), _ptr(aux_in), _ptr(obs), _ptr(mask), _ptr(sigma),
-        _ptr(q), _ptr(walk), _ptr(dt), _ptr(alive), _ptr(mean), _ptr(cov), _ptr(x_out), _ptr(aux_out), _ptr(stats)), "hode_ukf_step")
+    _call("ukf_step", dt_, B, 1 if predict else 0, int(link), (C.c_int32 * PF_MAX_AUX)(*mode), gamma, wm0, wc0, wi, x_in, status, aux_in,
+          obs, mask, sigma, q, walk, dt, alive, mean, cov, x_out, aux_out, stats)
     return x_out, aux_out, stats
 
 
@@ -656,6 +607,26 @@ def _pred_check_state(state, N, what):
             raise HodeError(f"{what}: state[{k!r}] must be a contiguous device tensor of {N} {'int32' if k == 'n' else 'float64'}")
 
 
+def _dense_rows(y, S, N):
+    return y if y[0].is_contiguous() and (S == 1 or y.stride(0) == N) else y.contiguous()
+
+
+def _need_obs_mask(what, obs, mask, N, dtype, dev, whose):
+    if obs is not None and (obs.dtype != dtype or obs.numel() != N or not obs.is_contiguous() or obs.device != dev):
+        raise HodeError(f"{what}: obs must be a contiguous device tensor of N entries in {whose} dtype")
+    if mask is not None and (obs is None or mask.dtype != torch.uint8 or mask.numel() != N or not mask.is_contiguous()):
+        raise HodeError(f"{what}: mask must be uint8 with the shape of obs")
+
+
+def _status_rows(what, status, S, N, dev):
+    if status is None:
+        return None, N
+    status = status.to(device=dev, dtype=torch.int32).contiguous()
+    if status.dim() != 2 or status.shape[0] != S or status.shape[1] < 1 or N % status.shape[1]:
+        raise HodeError(f"{what}: status must be [n_draws, n_traj] with n_traj dividing N")
+    return status, N // status.shape[1]
+
+
 def pred_fold(y, state, obs=None, mask=None, sigma=None, status=None):
     """Fold the draws y [n_draws, ...] (N entries each, fp32 or fp64, used where it lies when its rows are dense) into `state`
     (pred_state) in draw order; obs [N] in y's dtype and mask uint8 [N] or None; sigma fp64 [n_draws, 6] on the device or None;
@@ -665,26 +636,15 @@ def pred_fold(y, state, obs=None, mask=None, sigma=None, status=None):
     N = state["n"].numel()
     if y.dim() < 2 or y.numel() != S * N:
         raise HodeError(f"pred_fold: y must be [n_draws, {N} entries]")
-    if not (y[0].is_contiguous() and (S == 1 or y.stride(0) == N)):
-        y = y.contiguous()
+    y = _dense_rows(y, S, N)
     _pred_check_state(state, N, "pred_fold")
-    row_len = N
-    if obs is not None and (obs.dtype != y.dtype or obs.numel() != N or not obs.is_contiguous() or obs.device != y.device):
-        raise HodeError("pred_fold: obs must be a contiguous device tensor of N entries in y's dtype")
-    if mask is not None and (obs is None or mask.dtype != torch.uint8 or mask.numel() != N or not mask.is_contiguous()):
-        raise HodeError("pred_fold: mask must be uint8 with the shape of obs")
+    _need_obs_mask("pred_fold", obs, mask, N, y.dtype, y.device, "y's")
     if sigma is not None:
         sigma = sigma.to(device=y.device, dtype=torch.float64).contiguous()
         if tuple(sigma.shape) != (S, 6):
             raise HodeError("pred_fold: sigma must be [n_draws, 6]")
-    if status is not None:
-        status = status.to(device=y.device, dtype=torch.int32).contiguous()
-        if status.dim() != 2 or status.shape[0] != S or status.shape[1] < 1 or N % status.shape[1]:
-            raise HodeError("pred_fold: status must be [n_draws, n_traj] with n_traj dividing N")
-        row_len = N // status.shape[1]
-    _check(getattr(load(), f"hode_pred_fold_{_sfx(y.dtype)}")(
-        _stream(), C.c_int(S), C.c_int64(N), _ptr(y), _ptr(obs), _ptr(mask), _ptr(sigma), _ptr(status), C.c_int64(row_len),
-        *[_ptr(state[k]) for k in PRED_STATE]), "hode_pred_fold")
+    status, row_len = _status_rows("pred_fold", status, S, N, y.device)
+    _call("pred_fold", y.dtype, S, N, y, obs, mask, sigma, status, row_len, *[state[k] for k in PRED_STATE])
 
 
 def pred_score(state, dtype, obs=None, mask=None, extra_var=None, thr=(0.0,)):
@@ -697,18 +657,13 @@ def pred_score(state, dtype, obs=None, mask=None, extra_var=None, thr=(0.0,)):
     nb = len(thr)
     if not 1 <= nb <= PRED_MAX_BINS:
         raise HodeError(f"pred_score: {nb} bins, the kernel takes 1..{PRED_MAX_BINS} (HODE_PRED_MAX_BINS)")
-    if obs is not None and (obs.dtype != dtype or obs.numel() != N or not obs.is_contiguous() or obs.device != dev):
-        raise HodeError("pred_score: obs must be a contiguous device tensor of N entries in the working dtype")
-    if mask is not None and (obs is None or mask.dtype != torch.uint8 or mask.numel() != N or not mask.is_contiguous()):
-        raise HodeError("pred_score: mask must be uint8 with the shape of obs")
+    _need_obs_mask("pred_score", obs, mask, N, dtype, dev, "the working")
     K = PRED_FIXED_COLS + 2 * nb
     out = [torch.empty(N, dtype=dtype, device=dev) for _ in range(3)]
     table = torch.empty(6, K, dtype=torch.float64, device=dev)
     work = torch.empty(PRED_SCORE_BLOCKS * 6 * K, dtype=torch.float64, device=dev)
-    _check(getattr(load(), f"hode_pred_score_{_sfx(dtype)}")(
-        _stream(), C.c_int64(N), *[_ptr(state[k]) for k in PRED_STATE], _ptr(obs), _ptr(mask), _six(extra_var),
-        (C.c_double * nb)(*[float(x) for x in thr]), C.c_int(nb), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(table), _ptr(work)),
-        "hode_pred_score")
+    _call("pred_score", dtype, N, *[state[k] for k in PRED_STATE], obs, mask, _six(extra_var), (C.c_double * nb)(*[float(x) for x in thr]),
+          nb, *out, table, work)
     return out[0], out[1], out[2], table
 
 
@@ -718,7 +673,7 @@ PRED_MAX_LEVELS, PRED_BAND_COLS = 16, 4
 def pred_tail_state(N, K, dtype, device):
     """A fresh tail state of N entries that keeps the K smallest and the K largest values of each (include/hode.h "Posterior
     bands"): cnt = 0; the buffers lo, hi [K, N] in `dtype` need no initialisation."""
-    _sfx(dtype)
+    _need_real(dtype)
     if int(N) < 1 or int(K) < 1:
         raise HodeError("pred_tail_state: N >= 1 and K >= 1")
     return {"cnt": torch.zeros(int(N), dtype=torch.int32, device=device),
@@ -745,17 +700,9 @@ def pred_tails(y, tstate, status=None):
     S = y.shape[0]
     if y.dim() < 2 or y.numel() != S * N or y.dtype != tstate["lo"].dtype or y.device != tstate["cnt"].device:
         raise HodeError(f"pred_tails: y must be [n_draws, {N} entries] in the dtype and on the device of the state")
-    if not (y[0].is_contiguous() and (S == 1 or y.stride(0) == N)):
-        y = y.contiguous()
-    row_len = N
-    if status is not None:
-        status = status.to(device=y.device, dtype=torch.int32).contiguous()
-        if status.dim() != 2 or status.shape[0] != S or status.shape[1] < 1 or N % status.shape[1]:
-            raise HodeError("pred_tails: status must be [n_draws, n_traj] with n_traj dividing N")
-        row_len = N // status.shape[1]
-    _check(getattr(load(), f"hode_pred_tails_{_sfx(y.dtype)}")(
-        _stream(), C.c_int(S), C.c_int64(N), _ptr(y), _ptr(status), C.c_int64(row_len), C.c_int(K), _ptr(tstate["cnt"]),
-        _ptr(tstate["lo"]), _ptr(tstate["hi"])), "hode_pred_tails")
+    y = _dense_rows(y, S, N)
+    status, row_len = _status_rows("pred_tails", status, S, N, y.device)
+    _call("pred_tails", y.dtype, S, N, y, status, row_len, K, tstate["cnt"], tstate["lo"], tstate["hi"])
 
 
 def pred_quantiles(tstate, levels, obs=None, mask=None, band=False):
@@ -770,10 +717,7 @@ def pred_quantiles(tstate, levels, obs=None, mask=None, band=False):
         raise HodeError(f"pred_quantiles: {len(lv)} levels, the kernel takes 1..{PRED_MAX_LEVELS} (HODE_PRED_MAX_LEVELS)")
     if not all(0.0 < q < 1.0 for q in lv) or any(b <= a for a, b in zip(lv, lv[1:])):
         raise HodeError("pred_quantiles: levels must lie strictly inside (0, 1) and ascend")
-    if obs is not None and (obs.dtype != dtype or obs.numel() != N or not obs.is_contiguous() or obs.device != dev):
-        raise HodeError("pred_quantiles: obs must be a contiguous device tensor of N entries in the state's dtype")
-    if mask is not None and (obs is None or mask.dtype != torch.uint8 or mask.numel() != N or not mask.is_contiguous()):
-        raise HodeError("pred_quantiles: mask must be uint8 with the shape of obs")
+    _need_obs_mask("pred_quantiles", obs, mask, N, dtype, dev, "the state's")
     table = work = None
     if band:
         if obs is None or N % 6 or not lv[0] < 0.5 < lv[-1]:
@@ -781,9 +725,8 @@ def pred_quantiles(tstate, levels, obs=None, mask=None, band=False):
         table = torch.empty(6, PRED_BAND_COLS, dtype=torch.float64, device=dev)
         work = torch.empty(PRED_SCORE_BLOCKS * 6 * PRED_BAND_COLS, dtype=torch.float64, device=dev)
     out = torch.empty(len(lv), N, dtype=dtype, device=dev)
-    _check(getattr(load(), f"hode_pred_quantiles_{_sfx(dtype)}")(
-        _stream(), C.c_int64(N), C.c_int(K), _ptr(tstate["cnt"]), _ptr(tstate["lo"]), _ptr(tstate["hi"]), C.c_int(len(lv)),
-        (C.c_double * len(lv))(*lv), _ptr(out), _ptr(obs), _ptr(mask), _ptr(table), _ptr(work)), "hode_pred_quantiles")
+    _call("pred_quantiles", dtype, N, K, tstate["cnt"], tstate["lo"], tstate["hi"], len(lv), (C.c_double * len(lv))(*lv), out, obs, mask,
+          table, work)
     return out, table
 
 
@@ -839,26 +782,15 @@ def pred_loo_fold(y, lstate, obs, mask, sigma, status=None):
     S = y.shape[0]
     if y.dim() < 2 or y.numel() != S * N or y.device != lstate["cnt"].device:
         raise HodeError(f"pred_loo_fold: y must be [n_draws, {N} entries] on the device of the state")
-    if not (y[0].is_contiguous() and (S == 1 or y.stride(0) == N)):
-        y = y.contiguous()
+    y = _dense_rows(y, S, N)
     if obs is None or sigma is None:
         raise HodeError("pred_loo_fold: obs and sigma are required (without observation noise there is no likelihood)")
-    if obs.dtype != y.dtype or obs.numel() != N or not obs.is_contiguous() or obs.device != y.device:
-        raise HodeError("pred_loo_fold: obs must be a contiguous device tensor of N entries in y's dtype")
-    if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != N or not mask.is_contiguous()):
-        raise HodeError("pred_loo_fold: mask must be uint8 with the shape of obs")
+    _need_obs_mask("pred_loo_fold", obs, mask, N, y.dtype, y.device, "y's")
     sigma = sigma.to(device=y.device, dtype=torch.float64).contiguous()
     if tuple(sigma.shape) != (S, 6):
         raise HodeError("pred_loo_fold: sigma must be [n_draws, 6]")
-    row_len = N
-    if status is not None:
-        status = status.to(device=y.device, dtype=torch.int32).contiguous()
-        if status.dim() != 2 or status.shape[0] != S or status.shape[1] < 1 or N % status.shape[1]:
-            raise HodeError("pred_loo_fold: status must be [n_draws, n_traj] with n_traj dividing N")
-        row_len = N // status.shape[1]
-    _check(getattr(load(), f"hode_pred_loo_fold_{_sfx(y.dtype)}")(
-        _stream(), C.c_int(S), C.c_int64(N), _ptr(y), _ptr(obs), _ptr(mask), _ptr(sigma), _ptr(status), C.c_int64(row_len), C.c_int(K),
-        *[_ptr(lstate[k]) for k in PRED_LOO_STATE]), "hode_pred_loo_fold")
+    status, row_len = _status_rows("pred_loo_fold", status, S, N, y.device)
+    _call("pred_loo_fold", y.dtype, S, N, y, obs, mask, sigma, status, row_len, K, *[lstate[k] for k in PRED_LOO_STATE])
 
 
 def pred_loo_fit_rows(K):
@@ -872,7 +804,7 @@ def pred_loo_finish(lstate, dtype, r_eff=1.0):
     undefined, and the table fp64 [6, PRED_LOO_COLS] of include/hode.h).  r_eff: the relative efficiency of the draws, a host
     scalar in (0, 1].  The state's top is sorted in place and stays valid for further pred_loo_fold calls."""
     N, K = _pred_check_loo_state(lstate, "pred_loo_finish")
-    _sfx(dtype)
+    _need_real(dtype)
     r_eff = float(r_eff)
     if not 0.0 < r_eff <= 1.0:
         raise HodeError("pred_loo_finish: r_eff must lie in (0, 1]")
@@ -881,9 +813,8 @@ def pred_loo_finish(lstate, dtype, r_eff=1.0):
     table = torch.empty(6, PRED_LOO_COLS, dtype=torch.float64, device=dev)
     fit = torch.empty(pred_loo_fit_rows(K), N, dtype=torch.float64, device=dev)
     work = torch.empty(PRED_SCORE_BLOCKS * 6 * PRED_LOO_COLS, dtype=torch.float64, device=dev)
-    _check(getattr(load(), f"hode_pred_loo_finish_{_sfx(dtype)}")(
-        _stream(), C.c_int64(N), C.c_int(K), C.c_double(r_eff), *[_ptr(lstate[k]) for k in PRED_LOO_STATE],
-        *[_ptr(out[k]) for k in PRED_LOO_OUTPUTS], _ptr(table), _ptr(fit), _ptr(work)), "hode_pred_loo_finish")
+    _call("pred_loo_finish", dtype, N, K, r_eff, *[lstate[k] for k in PRED_LOO_STATE], *[out[k] for k in PRED_LOO_OUTPUTS], table, fit,
+          work)
     return out, table
 
 
@@ -898,46 +829,33 @@ def pred_loo_top_values(lstate):
 
 
 def hmc_refresh(C_, D, ld, seed, it, jitter, minv, log_eps, z, g, U, p, z0, g0, U0, ke0, eps, failed):
-    _check(getattr(load(), f"hode_hmc_refresh_{_sfx(z.dtype)}")(
-        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_uint64(seed), C.c_uint32(it), C.c_double(jitter), _ptr(minv),
-        _ptr(log_eps), _ptr(z), _ptr(g), _ptr(U), _ptr(p), _ptr(z0), _ptr(g0), _ptr(U0), _ptr(ke0), _ptr(eps), _ptr(failed)),
-        "hode_hmc_refresh")
+    _call("hmc_refresh", z.dtype, C_, D, ld, seed, it, jitter, minv, log_eps, z, g, U, p, z0, g0, U0, ke0, eps, failed)
 
 
 def hmc_leapfrog(C_, D, ld, flags, kick, eps, minv, z, p, g, gnn, gode, P, loss_sum, lik_scale, status, n_traj, U, ke, failed,
                  ode_mask, mu, sd, sample_nn, nn_p, ode_p):
-    _check(getattr(load(), f"hode_hmc_leapfrog_{_sfx(z.dtype)}")(
-        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(flags), C.c_double(kick), _ptr(eps), _ptr(minv), _ptr(z), _ptr(p),
-        _ptr(g), _ptr(gnn), _ptr(gode), C.c_int(P), _ptr(loss_sum), C.c_double(lik_scale), _ptr(status), C.c_int(n_traj), _ptr(U),
-        _ptr(ke), _ptr(failed), C.c_uint32(ode_mask), _ptr(mu), _ptr(sd), C.c_int(int(sample_nn)), _ptr(nn_p), _ptr(ode_p)),
-        "hode_hmc_leapfrog")
+    _call("hmc_leapfrog", z.dtype, C_, D, ld, flags, kick, eps, minv, z, p, g, gnn, gode, P, loss_sum, lik_scale, status, n_traj, U, ke,
+          failed, ode_mask, mu, sd, int(sample_nn), nn_p, ode_p)
 
 
 def hmc_accept(C_, D, ld, mode, seed, it, target_accept, z, z0, g, g0, U, U0, ke0, ke, failed, log_eps, da, search, n_ode, mu, sd,
                draws=None, stats=None, n_slots=0, slot=-1):
-    _check(getattr(load(), f"hode_hmc_accept_{_sfx(z.dtype)}")(
-        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(mode), C.c_uint64(seed), C.c_uint32(it), C.c_double(target_accept),
-        _ptr(z), _ptr(z0), _ptr(g), _ptr(g0), _ptr(U), _ptr(U0), _ptr(ke0), _ptr(ke), _ptr(failed), _ptr(log_eps), _ptr(da),
-        _ptr(search), C.c_int(n_ode), _ptr(mu), _ptr(sd), _ptr(draws), _ptr(stats), C.c_int(n_slots), C.c_int(slot)), "hode_hmc_accept")
+    _call("hmc_accept", z.dtype, C_, D, ld, mode, seed, it, target_accept, z, z0, g, g0, U, U0, ke0, ke, failed, log_eps, da, search,
+          n_ode, mu, sd, draws, stats, n_slots, slot)
 
 
 def hmc_welford(C_, D, ld, flags, z, wf, minv):
-    _check(getattr(load(), f"hode_hmc_welford_{_sfx(minv.dtype)}")(
-        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(flags), _ptr(z), _ptr(wf), _ptr(minv)), "hode_hmc_welford")
+    _call("hmc_welford", minv.dtype, C_, D, ld, flags, z, wf, minv)
 
 
 def pop_params(A, B, K, ld, coords, ode_mask, mu0, sd0, tau0, tau_log_sd, ode_base, ode_p):
     """The population map of the first A rows of coords [., ld] into ode_p [A * B, 17] (include/hode.h "Population model")."""
-    _check(getattr(load(), f"hode_pop_params_{_sfx(coords.dtype)}")(
-        _stream(), C.c_int(A), C.c_int(B), C.c_int(K), C.c_int(ld), _ptr(coords), C.c_uint32(ode_mask), _ptr(mu0), _ptr(sd0), _ptr(tau0),
-        C.c_double(tau_log_sd), _ptr(ode_base), _ptr(ode_p)), "hode_pop_params")
+    _call("pop_params", coords.dtype, A, B, K, ld, coords, ode_mask, mu0, sd0, tau0, tau_log_sd, ode_base, ode_p)
 
 
 def pop_grad(A, B, K, ld, coords, gode, ode_mask, sd0, tau0, tau_log_sd, glik):
     """The transposed population map: gode [A * B, 17] -> the likelihood gradient glik [A, ld] of the first A rows of coords."""
-    _check(getattr(load(), f"hode_pop_grad_{_sfx(coords.dtype)}")(
-        _stream(), C.c_int(A), C.c_int(B), C.c_int(K), C.c_int(ld), _ptr(coords), _ptr(gode), C.c_uint32(ode_mask), _ptr(sd0), _ptr(tau0),
-        C.c_double(tau_log_sd), _ptr(glik)), "hode_pop_grad")
+    _call("pop_grad", coords.dtype, A, B, K, ld, coords, gode, ode_mask, sd0, tau0, tau_log_sd, glik)
 
 
 X0_LINK_IDENTITY, X0_LINK_LOG = 0, 1
@@ -947,53 +865,41 @@ def x0_params(A, B, n_lat, ld, off, coords, lat_mask, link, m, s, x0_base, x0_ou
               ode_p=None):
     """The initial-state map of the first A rows of coords [., ld] into x0_out [A * B, 6] and, with ode_p, the rows' global
     constants into ode_p [A, 17] (include/hode.h "Initial-state model")."""
-    _check(getattr(load(), f"hode_x0_params_{_sfx(coords.dtype)}")(
-        _stream(), C.c_int(A), C.c_int(B), C.c_int(n_lat), C.c_int(ld), C.c_int(off), _ptr(coords), C.c_uint32(lat_mask), C.c_int(link),
-        _ptr(m), _ptr(s), _ptr(x0_base), _ptr(x0_out), C.c_int(K), C.c_uint32(ode_mask), _ptr(mu), _ptr(sd), _ptr(ode_base),
-        _ptr(ode_p)), "hode_x0_params")
+    _call("x0_params", coords.dtype, A, B, n_lat, ld, off, coords, lat_mask, link, m, s, x0_base, x0_out, K, ode_mask, mu, sd, ode_base,
+          ode_p)
 
 
 def x0_grad(A, B, n_lat, ld, off, coords, lat_mask, link, m, s, gx0, glik, K=0, ode_mask=0, sd=None, gode=None):
     """The transposed initial-state map: gx0 [A * B, 6] (and gode [A, 17]) -> the entries of the likelihood gradient glik [A, ld]
     that the layer owns; nothing else of glik is touched."""
-    _check(getattr(load(), f"hode_x0_grad_{_sfx(coords.dtype)}")(
-        _stream(), C.c_int(A), C.c_int(B), C.c_int(n_lat), C.c_int(ld), C.c_int(off), _ptr(coords), C.c_uint32(lat_mask), C.c_int(link),
-        _ptr(m), _ptr(s), _ptr(gx0), C.c_int(K), C.c_uint32(ode_mask), _ptr(sd), _ptr(gode), _ptr(glik)), "hode_x0_grad")
+    _call("x0_grad", coords.dtype, A, B, n_lat, ld, off, coords, lat_mask, link, m, s, gx0, K, ode_mask, sd, gode, glik)
 
 
 NUTS_ROWS, NUTS_MAX_DEPTH = 15, 30
 
 
 def nuts_begin(C_, D, ld, z, p, g, U, U0, ke0, tree, dst, ist):
-    _check(getattr(load(), f"hode_nuts_begin_{_sfx(z.dtype)}")(
-        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), _ptr(z), _ptr(p), _ptr(g), _ptr(U), _ptr(U0), _ptr(ke0), _ptr(tree), _ptr(dst),
-        _ptr(ist)), "hode_nuts_begin")
+    _call("nuts_begin", z.dtype, C_, D, ld, z, p, g, U, U0, ke0, tree, dst, ist)
 
 
 def nuts_pre(C_, D, ld, seed, it, eps, minv, tree, ist, rank, ode_mask, mu, sd, sample_nn, P, nn_p, ode_p):
-    _check(getattr(load(), f"hode_nuts_pre_{_sfx(tree.dtype)}")(
-        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_uint64(seed), C.c_uint32(it), _ptr(eps), _ptr(minv), _ptr(tree), _ptr(ist),
-        _ptr(rank), C.c_uint32(ode_mask), _ptr(mu), _ptr(sd), C.c_int(int(sample_nn)), C.c_int(P), _ptr(nn_p), _ptr(ode_p)), "hode_nuts_pre")
+    _call("nuts_pre", tree.dtype, C_, D, ld, seed, it, eps, minv, tree, ist, rank, ode_mask, mu, sd, int(sample_nn), P, nn_p, ode_p)
 
 
 def nuts_post(C_, D, ld, max_depth, seed, it, eps, minv, tree, ckpt, dst, ist, rank, gnn, gode, P, loss_sum, lik_scale, status, n_traj,
               ode_mask, sd, sample_nn):
-    _check(getattr(load(), f"hode_nuts_post_{_sfx(tree.dtype)}")(
-        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(max_depth), C.c_uint64(seed), C.c_uint32(it), _ptr(eps), _ptr(minv),
-        _ptr(tree), _ptr(ckpt), _ptr(dst), _ptr(ist), _ptr(rank), _ptr(gnn), _ptr(gode), C.c_int(P), _ptr(loss_sum), C.c_double(lik_scale),
-        _ptr(status), C.c_int(n_traj), C.c_uint32(ode_mask), _ptr(sd), C.c_int(int(sample_nn))), "hode_nuts_post")
+    _call("nuts_post", tree.dtype, C_, D, ld, max_depth, seed, it, eps, minv, tree, ckpt, dst, ist, rank, gnn, gode, P, loss_sum,
+          lik_scale, status, n_traj, ode_mask, sd, int(sample_nn))
 
 
 def nuts_compact(C_, ist, rank, count):
-    _check(load().hode_nuts_compact(_stream(), C.c_int(C_), _ptr(ist), _ptr(rank), _ptr(count)), "hode_nuts_compact")
+    _call("nuts_compact", None, C_, ist, rank, count)
 
 
 def nuts_finish(C_, D, ld, adapt, target_accept, z, g, U, tree, dst, ist, log_eps, da, n_ode, mu, sd, draws=None, stats=None, n_slots=0,
                 slot=-1):
-    _check(getattr(load(), f"hode_nuts_finish_{_sfx(z.dtype)}")(
-        _stream(), C.c_int(C_), C.c_int(D), C.c_int(ld), C.c_int(int(adapt)), C.c_double(target_accept), _ptr(z), _ptr(g), _ptr(U),
-        _ptr(tree), _ptr(dst), _ptr(ist), _ptr(log_eps), _ptr(da), C.c_int(n_ode), _ptr(mu), _ptr(sd), _ptr(draws), _ptr(stats),
-        C.c_int(n_slots), C.c_int(slot)), "hode_nuts_finish")
+    _call("nuts_finish", z.dtype, C_, D, ld, int(adapt), target_accept, z, g, U, tree, dst, ist, log_eps, da, n_ode, mu, sd, draws,
+          stats, n_slots, slot)
 
 
 # --------------------------------------------------------------------------------------------- data side
@@ -1006,7 +912,7 @@ FOURGI_COLUMNS = ["subject_id", "time_hours", "time_minutes", "glucose_mmol_L", 
 def fourgi_default_params(patient_type="T2DM"):
     """The reference's parameter set (data/generate4GI.py:15-64) as a list of 26 floats (host call, no GPU needed)."""
     buf = (C.c_double * FOURGI_NPAR)()
-    _check(load().hode_4gi_default_params(C.c_int(_ptype(patient_type)), buf), "hode_4gi_default_params")
+    _check(load().hode_4gi_default_params(_ptype(patient_type), buf), "hode_4gi_default_params")      # a host call: no stream
     return list(buf)
 
 
@@ -1050,11 +956,8 @@ def fourgi_generate(bsl, T, interval_min, meal_time, meal_size, patient_type="T2
         z = z_tcb.to(device=dev, dtype=torch.float64).contiguous()
     table = torch.empty(B * T, 9, dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    _check(load().hode_4gi_generate_f64(
-        _stream(), C.c_int(B), C.c_int(T), C.c_double(interval_min), C.c_int(_ptype(patient_type)), _par_host(par),
-        _ptr(bsl), C.c_int(n_meals), _ptr(mt if n_meals else None), _ptr(ms if n_meals else None), C.c_int(int(mt.dim() == 2)),
-        _ptr(z), C.c_double(noise_cv), C.c_int64(subject0), C.c_double(rtol), C.c_double(atol), C.c_int(max_steps),
-        _ptr(table), _ptr(status)), "hode_4gi_generate_f64")
+    _call("4gi_generate_f64", None, B, T, interval_min, _ptype(patient_type), _par_host(par), bsl, n_meals, mt if n_meals else None,
+          ms if n_meals else None, int(mt.dim() == 2), z, noise_cv, subject0, rtol, atol, max_steps, table, status)
     return table, status
 
 
@@ -1067,28 +970,31 @@ def fourgi_rhs(bsl, y, meal, patient_type="T2DM", par=None):
     meal = meal.to(device=dev, dtype=torch.float64).contiguous().view(-1)
     assert bsl.shape[0] == B and meal.shape[0] == B
     d = torch.empty_like(y)
-    _check(load().hode_4gi_rhs_f64(_stream(), C.c_int(B), C.c_int(_ptype(patient_type)), _par_host(par), _ptr(bsl), _ptr(y),
-                                   _ptr(meal), _ptr(d)), "hode_4gi_rhs_f64")
+    _call("4gi_rhs_f64", None, B, _ptype(patient_type), _par_host(par), bsl, y, meal, d)
     return d
+
+
+def _window_args(table, row0, seq_len, check_bounds):
+    _need_gpu(table)
+    if table.dtype != torch.float64 or table.dim() != 2:
+        raise HodeError("table must be a 2-D float64 tensor")
+    row0 = row0.to(device=table.device, dtype=torch.int64).contiguous()
+    N, S = row0.numel(), int(seq_len)
+    # checked on the host BEFORE the launch (two device reductions + a sync); callers that built row0 from the table's
+    # own subject ranges (GlucoseDataset) pass check_bounds=False
+    if check_bounds and N and (int(row0.min()) < 0 or int(row0.max()) + S > table.shape[0]):
+        raise HodeError("window outside the table")
+    return table.contiguous(), row0, N, S, table.device
 
 
 def fourgi_window_moments(table, cols, row0, seq_len, check_bounds=True):
     """Mergeable statistics of one shard's windows -> tensor[13] = {count, mean[6], M2[6]} on the device."""
-    _need_gpu(table)
-    dev = table.device
-    if table.dtype != torch.float64 or table.dim() != 2:
-        raise HodeError("table must be a 2-D float64 tensor")
-    table = table.contiguous()
-    row0 = row0.to(device=dev, dtype=torch.int64).contiguous()
-    N, S = row0.numel(), int(seq_len)
-    if check_bounds and N and (int(row0.min()) < 0 or int(row0.max()) + S > table.shape[0]):
-        raise HodeError("window outside the table")
+    table, row0, N, S, dev = _window_args(table, row0, seq_len, check_bounds)
     mom = torch.empty(13, dtype=torch.float64, device=dev)
     scratch = torch.empty(FOURGI_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
-    g = lambda k: C.c_int(int(cols.get(k, -1)))
-    _check(load().hode_4gi_window_moments_f64(_stream(), _ptr(table), C.c_int(table.shape[1]), g("glucose"), g("insulin"),
-                                              g("glucagon"), g("glp1"), g("ge"), g("ffa"), _ptr(row0), C.c_int64(N),
-                                              C.c_int64(S), _ptr(mom), _ptr(scratch)), "hode_4gi_window_moments_f64")
+    g = lambda k: int(cols.get(k, -1))                                                            # noqa: E731
+    _call("4gi_window_moments_f64", None, table, table.shape[1], g("glucose"), g("insulin"), g("glucagon"), g("glp1"), g("ge"), g("ffa"),
+          row0, N, S, mom, scratch)
     return mom
 
 
@@ -1114,17 +1020,7 @@ def combine_moments(moments):
 def fourgi_windows(table, cols, time_div, row0, seq_len, normalize=True, mean_std=None, check_bounds=True):
     """K8.  table[rows,ncols] fp64 (device); cols: dict time/glucose/insulin/glucagon/glp1 (+ optional ge/ffa/meal/tvns)
     -> column index; row0[N] int64 (device).  -> states[N,S,6], meal[N,S], tvns[N,S], time[N,S] (fp32), mean_std[12] (fp64)."""
-    _need_gpu(table)
-    dev = table.device
-    if table.dtype != torch.float64 or table.dim() != 2:
-        raise HodeError("table must be a 2-D float64 tensor")
-    table = table.contiguous()
-    row0 = row0.to(device=dev, dtype=torch.int64).contiguous()
-    N, S = row0.numel(), int(seq_len)
-    # checked on the host BEFORE the launch (two device reductions + a sync); callers that built row0 from the table's
-    # own subject ranges (GlucoseDataset) pass check_bounds=False
-    if check_bounds and N and (int(row0.min()) < 0 or int(row0.max()) + S > table.shape[0]):
-        raise HodeError("window outside the table")
+    table, row0, N, S, dev = _window_args(table, row0, seq_len, check_bounds)
     states = torch.empty(N, S, 6, dtype=torch.float32, device=dev)
     meal, tvns, time = (torch.empty(N, S, dtype=torch.float32, device=dev) for _ in range(3))
     if mean_std is not None:                            # statistics given (HODE_4GI_NORM_GIVEN)
@@ -1136,10 +1032,7 @@ def fourgi_windows(table, cols, time_div, row0, seq_len, normalize=True, mean_st
         mean_std = torch.empty(12, dtype=torch.float64, device=dev)
         normalize = int(bool(normalize))
     scratch = torch.empty(FOURGI_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
-    g = lambda k: C.c_int(int(cols.get(k, -1)))
-    _check(load().hode_4gi_windows_f32(
-        _stream(), _ptr(table), C.c_int(table.shape[1]), g("time"), C.c_double(time_div), g("glucose"), g("insulin"),
-        g("glucagon"), g("glp1"), g("ge"), g("ffa"), g("meal"), g("tvns"), _ptr(row0), C.c_int64(N), C.c_int64(S),
-        C.c_int(normalize), _ptr(states), _ptr(meal), _ptr(tvns), _ptr(time), _ptr(mean_std), _ptr(scratch)),
-        "hode_4gi_windows_f32")
+    g = lambda k: int(cols.get(k, -1))                                                            # noqa: E731
+    _call("4gi_windows_f32", None, table, table.shape[1], g("time"), time_div, g("glucose"), g("insulin"), g("glucagon"), g("glp1"),
+          g("ge"), g("ffa"), g("meal"), g("tvns"), row0, N, S, normalize, states, meal, tvns, time, mean_std, scratch)
     return states, meal, tvns, time, mean_std
