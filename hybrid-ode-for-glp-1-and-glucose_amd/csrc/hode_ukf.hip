@@ -15,8 +15,7 @@
 // that depends on the patient -- the seen states, a lost patient, a wave past the last patient -- is predicated) and no wave
 // returns in front of one.  Floating-point contraction is off (an a * b + c here is two roundings), there are no atomics: the
 // same call gives the same bits, and a patient's bits depend neither on B nor on its row.
-#include "hode_chains.h"
-#include <cmath>
+#include "hode_ukf_linalg.h"
 #include <limits>
 
 #pragma clang fp contract(off)
@@ -26,7 +25,6 @@ namespace {
 
 constexpr int kUkfPatients = kThreads / 64;
 constexpr double kLog2Pi = 1.8378770664093453;
-constexpr double kEps = 2.220446049250313e-16;                 // 2^-52
 
 template <typename R> struct UkfArgs {
     int B, predict, link, n_par;
@@ -54,48 +52,6 @@ __device__ __forceinline__ int nth_seen(uint32_t m, int a)
             --a;
         }
     return 0;
-}
-
-// The lower Cholesky factor L of the n x n matrix A (row-major, both in this wave's LDS), column by column without pivoting; the
-// upper triangle of L is written as zeros.  pivot_j = A_jj - sum_{k<j} L_jk^2, the sum from k = 0 in order; a pivot
-// <= n 2^-52 |A_jj| gives a zero column.  A non-finite pivot: returns true (L is then arbitrary, but every entry is written).
-__device__ __forceinline__ bool ukf_chol(const double *A, double *L, int n, int lane)
-{
-    bool bad = false;
-    for (int j = 0; j < n; ++j) {
-        double piv = A[j * n + j];
-        for (int k = 0; k < j; ++k) piv -= L[j * n + k] * L[j * n + k];
-        const bool finite = __builtin_isfinite(piv);
-        bad = bad || !finite;
-        const bool zero = !finite || !(piv > (double)n * kEps * fabs(A[j * n + j]));
-        const double root = zero ? 1.0 : sqrt(piv);
-        for (int i = lane; i < n; i += 64) {
-            double t = 0.0;
-            if (i == j && !zero) t = root;
-            if (i > j && !zero) {
-                t = A[i * n + j];
-                for (int k = 0; k < j; ++k) t -= L[i * n + k] * L[j * n + k];
-                t = t / root;
-            }
-            L[i * n + j] = t;
-        }
-        __syncthreads();
-    }
-    return bad;
-}
-
-// Z [K][n] <- the sigma points of (M, L): row 0 the mean, rows 1..n the mean + gamma * column, rows n+1..2n the mean - it
-__device__ __forceinline__ void ukf_draw(double *Z, const double *M, const double *L, int n, double gamma, int lane)
-{
-    const int K = 2 * n + 1;
-    for (int e = lane; e < K * n; e += 64) {
-        const int k = e / n, j = e - k * n;
-        double v = M[j];
-        if (k >= 1 && k <= n) v = v + gamma * L[j * n + (k - 1)];
-        else if (k > n) v = v - gamma * L[j * n + (k - n - 1)];
-        Z[e] = v;
-    }
-    __syncthreads();
 }
 
 template <typename R> __global__ __launch_bounds__(kThreads) void ukf_step_kernel(const UkfArgs<R> a)

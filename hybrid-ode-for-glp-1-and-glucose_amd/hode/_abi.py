@@ -77,6 +77,14 @@ ABI = {
                 "int32_t*, double* x2, R* x2, double*)",
 }
 
+# The extension headers: entry points that libhode.so exports beside those of include/hode.h, declared in a header of their own
+# that includes hode.h.  {header under include/: a table as above}; tests/test_ukf_smooth_host.py holds this one to its header.
+EXTENSIONS = {
+    "hode_ukf_smooth.h": {
+        "ukf_smooth": "int(void*, int x3, const int32_t*, double x4, const R* x3, const double* x2, const int32_t*, const double* x3, double* x6)",
+    },
+}
+
 # the vocabulary of the header: anything else in a prototype is an error
 RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
 SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": C.c_float,
@@ -142,14 +150,18 @@ def ctypes_of(symbol, ret, words):
 
 SIGNATURES = {sym: (name, dtype) + ctypes_of(sym, ret, words) for sym, name, dtype, ret, words in expand()}
 SYMBOLS = list(SIGNATURES)                                            # every symbol include/hode.h declares
+EXT_SIGNATURES = {hdr: {sym: (name, dtype) + ctypes_of(sym, ret, words) for sym, name, dtype, ret, words in expand(table)}
+                  for hdr, table in EXTENSIONS.items()}
+EXT_SYMBOLS = {hdr: list(sigs) for hdr, sigs in EXT_SIGNATURES.items()}   # every symbol each extension header declares
 
 
 def bind(lib, path):
-    """Declare every symbol of the table on a loaded library.  Returns {(family, dtype or None): function}."""
+    """Declare every symbol of the table and of the extension tables on a loaded library.  Returns {(family, dtype or None): function}."""
     fns = {}
-    for sym, (name, dtype, restype, argtypes) in SIGNATURES.items():
-        if not hasattr(lib, sym):
-            raise HodeError(f"{path} does not export {sym}, which include/hode.h declares")
-        fn = fns[name, dtype] = getattr(lib, sym)
-        fn.restype, fn.argtypes = restype, argtypes
+    for hdr, sigs in [("hode.h", SIGNATURES)] + list(EXT_SIGNATURES.items()):
+        for sym, (name, dtype, restype, argtypes) in sigs.items():
+            if not hasattr(lib, sym):
+                raise HodeError(f"{path} does not export {sym}, which include/{hdr} declares")
+            fn = fns[name, dtype] = getattr(lib, sym)
+            fn.restype, fn.argtypes = restype, argtypes
     return fns

@@ -5,7 +5,7 @@ import os
 
 import torch
 
-from ._abi import SYMBOLS, HodeError, bind  # noqa: F401
+from ._abi import EXT_SYMBOLS, SYMBOLS, HodeError, bind  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("HODE_LIB") or os.path.join(_HERE, "libhode.so")   # HODE_LIB: development builds
@@ -587,6 +587,50 @@ def ukf_step(x_in, aux_in, mode, obs, sigma, q, walk, dt, alive, mean, cov, weig
     _call("ukf_step", dt_, B, 1 if predict else 0, int(link), (C.c_int32 * PF_MAX_AUX)(*mode), gamma, wm0, wc0, wi, x_in, status, aux_in,
           obs, mask, sigma, q, walk, dt, alive, mean, cov, x_out, aux_out, stats)
     return x_out, aux_out, stats
+
+
+def ukf_smooth(history, ode_history, propagated, mean, cov, alive, mode, q, walk, dt, weights, link=1, out=None):
+    """The unscented RTS smoother over a stored filter (include/hode_ukf_smooth.h): history / propagated [S, B, K, 6]
+    fp32 or fp64 on the device (the points every step emitted, and the rows every step was handed) and ode_history [S, B, K, 17] of
+    their dtype; mean fp64 [S, B, n], cov fp64 [S, B, n, n] and alive int32 [S, B] after every step; mode: 17 ints on the HOST
+    (PF_MOVE), K = 2 n + 1 with n = 6 + the non-zero ones; q fp64 [6], walk fp64 [17], dt fp64 [S, B] on the device;
+    weights = (gamma, wm0, wc0, wi).  `out`: the six buffers to write into, else they are allocated.
+    Returns (mean_s [S, B, n], cov_s [S, B, n, n], gain [S-1, B, n, n], pred_mean [S-1, B, n], pred_cov [S-1, B, n, n],
+    moments [S, B, 12]), all fp64."""
+    _need_gpu(history)
+    mode = [int(v) for v in (mode.tolist() if hasattr(mode, "tolist") else mode)]
+    if len(mode) != PF_MAX_AUX or any(v not in (0, 1, 2) for v in mode):
+        raise HodeError(f"ukf_smooth: mode must be {PF_MAX_AUX} host integers in 0..2 (PF_MOVE)")
+    n = 6 + sum(1 for v in mode if v)
+    K = 2 * n + 1
+    if history.dim() != 4 or tuple(history.shape[2:]) != (K, 6) or not history.is_contiguous():
+        raise HodeError(f"ukf_smooth: history must be a contiguous [S, B, K, 6] with K = 2 (6 + P) + 1 = {K}")
+    S, B = int(history.shape[0]), int(history.shape[1])
+    dev, dt_ = history.device, history.dtype
+    if S < 1 or B < 1:
+        raise HodeError("ukf_smooth: history must hold at least one step of at least one patient")
+    if propagated.shape != history.shape or propagated.dtype != dt_ or propagated.device != dev or not propagated.is_contiguous():
+        raise HodeError("ukf_smooth: propagated must be a contiguous [S, B, K, 6] of history's dtype")
+    if (tuple(ode_history.shape) != (S, B, K, PF_MAX_AUX) or ode_history.dtype != dt_ or ode_history.device != dev
+            or not ode_history.is_contiguous()):
+        raise HodeError(f"ukf_smooth: ode_history must be a contiguous [S, B, K, {PF_MAX_AUX}] of history's dtype")
+    _need_vectors("ukf_smooth", dev, torch.float64, (("mean", mean, S * B * n), ("cov", cov, S * B * n * n), ("q", q, 6),
+                                                     ("walk", walk, PF_MAX_AUX), ("dt", dt, S * B)))
+    _need_vectors("ukf_smooth", dev, torch.int32, (("alive", alive, S * B),))
+    gamma, wm0, wc0, wi = (float(v) for v in weights)
+    shapes = ((S, B, n), (S, B, n, n), (S - 1, B, n, n), (S - 1, B, n), (S - 1, B, n, n), (S, B, 12))
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=torch.float64, device=dev) for sh in shapes)
+    if len(out) != 6 or not all(_is_buffer(t, torch.float64, dev, sh) for t, sh in zip(out, shapes)):
+        raise HodeError("ukf_smooth: out must be (mean_s [S, B, n], cov_s [S, B, n, n], gain [S-1, B, n, n], pred_mean [S-1, B, n], "
+                        "pred_cov [S-1, B, n, n], moments [S, B, 12]), contiguous fp64 on history's device")
+    ins = {t.data_ptr() for t in (history, ode_history, propagated, mean, cov, alive, q, walk, dt)}
+    outs = [t.data_ptr() for t in out if t.numel()]
+    if any(p in ins for p in outs) or len(set(outs)) != len(outs):
+        raise HodeError("ukf_smooth: an output may not alias an input or another output")
+    _call("ukf_smooth", dt_, S, B, int(link), (C.c_int32 * PF_MAX_AUX)(*mode), gamma, wm0, wc0, wi, history, ode_history, propagated,
+          mean, cov, alive, q, walk, dt, *out)
+    return tuple(out)
 
 
 PRED_MAX_BINS, PRED_FIXED_COLS, PRED_SCORE_BLOCKS = 32, 16, 128

@@ -8,7 +8,9 @@ filter").
                  of the step kernel: the unscented moments of the propagated points, the measurement update, the next points.
                  Nothing is read back to the host inside the loop, and there is no seed: the same call gives the same bits.
     UKFResult    the filtered moments, NIS, log-evidence increments, the final mean / covariance / sigma points; `forecast`
-                 continues the same loop without observations.
+                 continues the same loop without observations; `smooth` (store_history=True) is the unscented Rauch-Tung-Striebel
+                 pass over the stored run (csrc/hode_ukf_smooth.hip): a UKFSmoothResult, the state at
+                 every step given the whole record.
 
 The state model is `run_filter`'s: between two steps a state follows the deterministic solve; over a step of length dt it gains
 noise of standard deviation process_noise * sqrt(dt) -- additive, or on the logarithm with the -s^2 / 2 drift that keeps the
@@ -24,7 +26,7 @@ import hode
 from .filter import (LearnedParameters, ParameterLearning, _check_data, _check_steps, _default_steps, _inputs, _six_nonneg)
 from .observation import ObservationModel
 
-__all__ = ["UKFResult", "run_ukf"]
+__all__ = ["UKFResult", "UKFSmoothResult", "run_ukf"]
 
 
 class _Engine:
@@ -51,7 +53,8 @@ class _Engine:
         index of `idxs` (and, with init, one without a prediction at index 0, from the given mean [B, n] / cov [B, n, n]);
         obs [B, T, 6] / mask uint8 [B, T, 6] or None (no observations).  mean, cov and alive are updated in place.  Returns
         (x, ode_p, stats [S, B, 16], the mean [S, B, n] and the variances [S, B, n] in link space after every step, and with
-        store the history (sigma points [S, B, K, 6], their constants [S, B, K, 17], covariances [S, B, n, n]), else None)."""
+        store the history (sigma points [S, B, K, 6], their constants [S, B, K, 17], covariances [S, B, n, n], the rows x_in every
+        step was handed [S, B, K, 6], its dt [S, B]), else None)."""
         B, K, n, dev, dtype = self.B, self.K, self.n, self.dev, self.dtype
         with torch.no_grad():
             nn_flat, _ = self.model._params_on(dev)
@@ -61,7 +64,8 @@ class _Engine:
             means = torch.empty(S, B, n, dtype=torch.float64, device=dev)
             variances = torch.empty(S, B, n, dtype=torch.float64, device=dev)
             hist = (torch.empty(S, B, K, 6, dtype=dtype, device=dev), torch.empty(S, B, K, 17, dtype=dtype, device=dev),
-                    torch.empty(S, B, n, n, dtype=torch.float64, device=dev)) if self.store else None
+                    torch.empty(S, B, n, n, dtype=torch.float64, device=dev), torch.empty(S, B, K, 6, dtype=dtype, device=dev),
+                    torch.empty(S, B, dtype=torch.float64, device=dev)) if self.store else None
             bufs, aux = [x, torch.empty_like(x)], [ode_p, torch.empty_like(ode_p)]
             nan_row = torch.full((B, 6), float("nan"), dtype=dtype, device=dev)
             per_patient = t.dim() == 2
@@ -83,6 +87,8 @@ class _Engine:
                     hist[0][s].copy_(bufs[1])
                     hist[1][s].copy_(aux[1])
                     hist[2][s].copy_(cov)
+                    hist[3][s].copy_(x_in)
+                    hist[4][s].copy_(dt)
                 bufs.reverse()
                 aux.reverse()
                 s += 1
@@ -120,9 +126,13 @@ class UKFResult:
                                  learned constant in link space and scale = the square root of its variance
       history [S, B, K, 6], ode_history [S, B, K, 17], mean_history [S, B, n], cov_history [S, B, n, n] (store_history=True,
                                  else None): the sigma points and their constants that every step emitted, and its moments in
-                                 link space"""
+                                 link space
+      propagated_history [S, B, K, 6], dt_history [S, B] (fp64) (store_history=True, else None): the rows every step was handed
+                                 -- the end of the solve from the points of the step before; at the first step of a run its
+                                 initial points -- and the dt it received.  The constants of the propagated points are
+                                 ode_history[s - 1]: a solve does not change them.  `smooth()` needs the history."""
 
-    def __init__(self, engine, stats, means, variances, step_index, times, x, ode_p, mean, cov, alive, hist=None):
+    def __init__(self, engine, stats, means, variances, step_index, times, x, ode_p, mean, cov, alive, hist=None, forecast=False):
         st = stats.permute(1, 0, 2)
         self.log_evidence_steps, self.nis = st[..., 0].contiguous(), st[..., 1].contiguous()
         self.n_seen, self.alive = st[..., 2].to(torch.int64), st[..., 3] > 0
@@ -130,7 +140,9 @@ class UKFResult:
         self.step_index, self.times = step_index, times
         self.sigma_points, self.ode_p, self.state_mean, self.state_cov = x, ode_p, mean, cov
         self._engine, self._alive = engine, alive
-        self.history, self.ode_history, self.cov_history = hist if hist is not None else (None, None, None)
+        self.history, self.ode_history, self.cov_history, self.propagated_history, self.dt_history = \
+            hist if hist is not None else (None,) * 5
+        self._forecast = forecast
         self.mean_history = means if hist is not None else None
         self.learned = None
         if engine.learn is not None:
@@ -168,7 +180,47 @@ class UKFResult:
         x, ode_p, stats, means, variances, hist = e.run(self.sigma_points.clone(), self.ode_p.clone(), mean, cov, alive, t, ins, None,
                                                         None, idxs, False)
         gi = torch.as_tensor(idxs, device=e.dev)
-        return UKFResult(e, stats, means, variances, gi, t[..., gi], x, ode_p, mean, cov, alive, hist)
+        return UKFResult(e, stats, means, variances, gi, t[..., gi], x, ode_p, mean, cov, alive, hist, forecast=True)
+
+    def smooth(self):
+        """The unscented Rauch-Tung-Striebel smoother over this run (store_history=True): the state at every step given the whole
+        record, where `mean` / `std` give it given the record up to that step.  Three kernel launches (csrc/hode_ukf_smooth.hip;
+        include/hode_ukf_smooth.h), nothing is read back to the host.  Returns a UKFSmoothResult."""
+        if self._forecast:
+            raise ValueError("smooth() is for the result of run_ukf: a forecast has no observations to look back from")
+        if self.history is None:
+            raise ValueError("smooth() needs the filter's history: run_ukf(..., store_history=True)")
+        e = self._engine
+        alive = self.alive.t().to(torch.int32).contiguous()
+        out = hode.capi.ukf_smooth(self.history, self.ode_history, self.propagated_history, self.mean_history, self.cov_history, alive,
+                                   e.mode, e.q, e.walk, self.dt_history, e.weights, link=e.link)
+        return UKFSmoothResult(e, self, *out)
+
+
+class UKFSmoothResult:
+    """The result of `UKFResult.smooth()`, tensors on the compute device; S, n and the coordinates as in the UKFResult it came from.
+      mean, std [B, S, 6]        the smoothed moments of the states in natural space: the unscented mean and standard deviation of
+                                 the sigma points of (state_mean, state_cov); at a patient's last step the filter's, bit for bit
+      state_mean [B, S, n], state_cov [B, S, n, n]   the smoothed moments in link space (fp64)
+      gain [B, S-1, n, n]        the smoother gain G_s = C_s (P-_{s+1})^-1 of every pair of steps
+      pred_mean [B, S-1, n], pred_cov [B, S-1, n, n]   the predicted moments m-, P- of step s + 1 that G_s was formed with
+      alive [B, S], step_index [S], times               carried over; from the step at which a patient was lost everything above is
+                                 NaN for it (and the gain into that step), and its last alive step is its terminal one
+      learned                    a LearnedParameters (run_ukf(learn=...), else None): per step, the smoothed location and scale of
+                                 every learned constant in link space, in the caller's order"""
+
+    def __init__(self, engine, res, mean_s, cov_s, gain, pred_mean, pred_cov, moments):
+        mo = moments.permute(1, 0, 2)
+        self.mean, self.std = mo[..., :6].contiguous(), mo[..., 6:].clamp_min(0).sqrt()
+        self.state_mean, self.state_cov = mean_s.transpose(0, 1).contiguous(), cov_s.transpose(0, 1).contiguous()
+        self.gain, self.pred_mean, self.pred_cov = (v.transpose(0, 1).contiguous() for v in (gain, pred_mean, pred_cov))
+        self.alive, self.step_index, self.times = res.alive, res.step_index, res.times
+        self.learned = None
+        if engine.learn is not None:
+            lr = engine.learn
+            at = torch.as_tensor(6 + np.argsort(np.argsort(lr.columns)), device=mean_s.device)
+            self.learned = LearnedParameters(lr.names, lr.link, self.state_mean[..., at].contiguous(),
+                                             self.state_cov.diagonal(dim1=2, dim2=3)[..., at].clamp_min(0).sqrt())
 
 
 def run_ukf(model, data, process_noise=0.05, noise_link="log", noise_sigma=1.0, initial_spread=0.1, learn=None, alpha=1.0, beta=0.0,
@@ -187,7 +239,8 @@ def run_ukf(model, data, process_noise=0.05, noise_link="log", noise_sigma=1.0, 
     initial_spread > 0 or walk > 0.  Its `discount` is NOT used: a Kalman filter learns a constant through its cross-covariance
     with the states, and there is no shrinkage.
     alpha, beta, kappa: the scaled unscented transform (hode.capi.ukf_weights); the defaults 1, 0, 1 give all-positive weights,
-    so no covariance sum can go indefinite by its weights.  store_history: keep what every step emitted (UKFResult.history).
+    so no covariance sum can go indefinite by its weights.  store_history: keep what every step emitted and was handed
+    (UKFResult.history, .propagated_history): what `UKFResult.smooth()` works from.
     Returns a UKFResult."""
     from models.hybrid_ode_nn import _compute_device, _method
     if noise_link not in hode.capi.PF_LINK:
