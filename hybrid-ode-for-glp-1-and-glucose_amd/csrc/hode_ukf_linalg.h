@@ -1,7 +1,8 @@
-// hode_ukf_linalg.h -- the two pieces of per-wave linear algebra that the unscented filter's step (hode_ukf.hip) and its
-// smoother (hode_ukf_smooth.hip) share: the column Cholesky factor with its zero-column rule, and the sigma points of a mean and a
-// factor.  Both work on one wave's slice of LDS and end on a workgroup barrier, so every wave of the workgroup calls them with
-// the same n.  Contraction is off from here on in the including file: a * b + c below is two roundings.
+// hode_ukf_linalg.h -- the two pieces of per-wave linear algebra that the unscented filter's step (hode_ukf.hip), its smoother
+// (hode_ukf_smooth.hip) and the EM statistics over it (hode_ukf_em.hip) share: the column Cholesky factor with its zero-column
+// rule, and the sigma points of a mean and a factor.  Both work on one wave's slice of LDS and end on a workgroup barrier, so
+// every wave of the workgroup calls them with the same n.  Contraction is off from here on in the including file: a * b + c below
+// is two roundings.  At the end, the two host helpers that size a launch whose waves each own a slice of the dynamic LDS.
 #pragma once
 #include "hode_chains.h"
 #include <cmath>
@@ -53,6 +54,26 @@ __device__ __forceinline__ void ukf_draw(double *Z, const double *M, const doubl
         Z[e] = v;
     }
     __syncthreads();
+}
+
+// ---- launching a kernel whose waves each own a slice of the dynamic LDS (the smoother, the EM statistics)
+constexpr size_t kCuLds = 160 * 1024;                           // the LDS of a gfx950 CU: what a workgroup may ask for
+
+// the waves of a workgroup whose slices of `doubles` doubles stay inside a CU's LDS
+inline int waves_for(int doubles)
+{
+    const size_t fit = kCuLds / ((size_t)doubles * sizeof(double));
+    return fit >= (size_t)(kThreads / 64) ? kThreads / 64 : fit < 1 ? 1 : (int)fit;
+}
+
+// (more than 64 KiB of dynamic LDS has to be asked for)
+template <typename F> bool lds_ok(F *kernel, size_t bytes)
+{
+    if (bytes <= 64 * 1024) return true;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess)
+        return true;
+    (void)hipGetLastError();
+    return false;
 }
 
 }  // namespace

@@ -24,8 +24,6 @@
 namespace hode {
 namespace {
 
-constexpr size_t kCuLds = 160 * 1024;                           // the LDS of a gfx950 CU: what a workgroup may ask for
-
 template <typename R> struct UkfSmoothArgs {
     int S, B, link, n_par;
     double gamma, wm0, wc0, wi;
@@ -236,23 +234,6 @@ template <typename R> __global__ __launch_bounds__(kThreads) void ukf_moments_ke
         a.moments[it * 12 + lane] = live ? mu : nan;
         a.moments[it * 12 + 6 + lane] = live ? var : nan;
     }
-}
-
-// the waves of a workgroup whose slices of `doubles` doubles stay inside a CU's LDS
-inline int waves_for(int doubles)
-{
-    const size_t fit = kCuLds / ((size_t)doubles * sizeof(double));
-    return fit >= (size_t)(kThreads / 64) ? kThreads / 64 : fit < 1 ? 1 : (int)fit;
-}
-
-// (more than 64 KiB of dynamic LDS has to be asked for)
-template <typename F> bool lds_ok(F *kernel, size_t bytes)
-{
-    if (bytes <= 64 * 1024) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess)
-        return true;
-    (void)hipGetLastError();
-    return false;
 }
 
 template <typename R>

@@ -78,10 +78,18 @@ ABI = {
 }
 
 # The extension headers: entry points that libhode.so exports beside those of include/hode.h, declared in a header of their own
-# that includes hode.h.  {header under include/: a table as above}; tests/test_ukf_smooth_host.py holds this one to its header.
+# that includes hode.h.  {header under include/: a table as above}; tests/test_ukf_smooth_host.py and tests/test_ukf_em_host.py
+# hold each to its header.
 EXTENSIONS = {
     "hode_ukf_smooth.h": {
         "ukf_smooth": "int(void*, int x3, const int32_t*, double x4, const R* x3, const double* x2, const int32_t*, const double* x3, double* x6)",
+    },
+    "hode_ukf_em.h": {
+        "ukf_em_points": "int(void*, int x3, const int32_t*, double, const double* x2, const int32_t*, const R*, R* x2, double*)",
+        "ukf_em_stats": "int(void*, int x3, const int32_t*, double x4, const R*, const int32_t*, const double* x4, const int32_t*, const R*, "
+                        "const uint8_t*, const double*, double*, int32_t*, double*, int32_t*)",
+        "ukf_em_mstep": "int(void*, int x3, const int32_t* x2, const double* x2, const int32_t*, const double*, const int32_t*, const double*, "
+                        "double* x4)",
     },
 }
 

@@ -633,6 +633,119 @@ def ukf_smooth(history, ode_history, propagated, mean, cov, alive, mode, q, walk
     return tuple(out)
 
 
+UKF_EM_SUMS, UKF_EM_FIT = 37, 29
+UKF_EM_SUM_AT = {"A": slice(0, 23), "N": 23, "D": 24, "R": slice(25, 31), "M": slice(31, 37)}      # the layout of `sums`
+
+
+def _em_head(what, mode, mean_s, cov_s, alive):
+    """(mode, S, B, n, K, device) of the smoothed run every EM entry starts from (include/hode_ukf_em.h)."""
+    _need_gpu(mean_s)
+    mode = [int(v) for v in (mode.tolist() if hasattr(mode, "tolist") else mode)]
+    if len(mode) != PF_MAX_AUX or any(v not in (0, 1, 2) for v in mode):
+        raise HodeError(f"{what}: mode must be {PF_MAX_AUX} host integers in 0..2 (PF_MOVE)")
+    n = 6 + sum(1 for v in mode if v)
+    if mean_s.dim() != 3 or mean_s.shape[2] != n or mean_s.shape[0] < 1 or mean_s.shape[1] < 1:
+        raise HodeError(f"{what}: mean_s must be [S, B, n] with n = 6 + P = {n}, S >= 1, B >= 1")
+    S, B = int(mean_s.shape[0]), int(mean_s.shape[1])
+    dev = mean_s.device
+    _need_vectors(what, dev, torch.float64, (("mean_s", mean_s, S * B * n), ("cov_s", cov_s, S * B * n * n)))
+    _need_vectors(what, dev, torch.int32, (("alive", alive, S * B),))
+    return mode, S, B, n, 2 * n + 1, dev
+
+
+def _em_distinct(what, ins, outs):
+    ins = {t.data_ptr() for t in ins if t is not None and t.numel()}
+    outs = [t.data_ptr() for t in outs if t.numel()]
+    if any(p in ins for p in outs) or len(set(outs)) != len(outs):
+        raise HodeError(f"{what}: an output may not alias an input or another output")
+
+
+def ukf_em_points(mean_s, cov_s, alive, ode_history, mode, weights, link=1, out=None):
+    """The sigma points of the smoothed moments of every pair's first step (include/hode_ukf_em.h): mean_s fp64 [S, B, n], cov_s
+    fp64 [S, B, n, n], alive int32 [S, B] and ode_history [S, B, K, 17] fp32 or fp64 on the device, step-major; mode: 17 ints on
+    the HOST (PF_MOVE); weights = (gamma, wm0, wc0, wi).  `out`: the three buffers to write into, else they are allocated.
+    Returns (x_em [S-1, B*K, 6], aux_em [S-1, B*K, 17] of ode_history's dtype, chol fp64 [S-1, B, n, n])."""
+    mode, S, B, n, K, dev = _em_head("ukf_em_points", mode, mean_s, cov_s, alive)
+    dt_ = ode_history.dtype
+    _need_real(dt_)
+    if tuple(ode_history.shape) != (S, B, K, PF_MAX_AUX) or ode_history.device != dev or not ode_history.is_contiguous():
+        raise HodeError(f"ukf_em_points: ode_history must be a contiguous [S, B, K, {PF_MAX_AUX}] with K = 2 n + 1 = {K}")
+    shapes = (((S - 1, B * K, 6), dt_), ((S - 1, B * K, PF_MAX_AUX), dt_), ((S - 1, B, n, n), torch.float64))
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=d, device=dev) for sh, d in shapes)
+    if len(out) != 3 or not all(_is_buffer(t, d, dev, sh) for t, (sh, d) in zip(out, shapes)):
+        raise HodeError("ukf_em_points: out must be (x_em [S-1, B*K, 6], aux_em [S-1, B*K, 17] of ode_history's dtype, chol fp64 "
+                        "[S-1, B, n, n]), contiguous on the device")
+    _em_distinct("ukf_em_points", (mean_s, cov_s, alive, ode_history), out)
+    _call("ukf_em_points", dt_, S, B, int(link), (C.c_int32 * PF_MAX_AUX)(*mode), float(weights[0]), mean_s, cov_s, alive, ode_history,
+          *out)
+    return tuple(out)
+
+
+def ukf_em_stats(prop_em, status, chol, mean_s, cov_s, gain, alive, obs, mask, moments, mode, weights, link=1, out=None):
+    """The expected squared residuals of one E-step (include/hode_ukf_em.h): prop_em [S-1, B*K, 6] fp32 or fp64, the end of the
+    solve of ukf_em_points' rows over every pair's segment, and status int32 [S-1, B*K]; chol as ukf_em_points gave it; mean_s,
+    cov_s, gain fp64 [S-1, B, n, n], moments fp64 [S, B, 12]: the smoother's; alive int32 [S, B]; obs [B, S, 6] of prop_em's dtype
+    (PATIENT-major: the record's rows at the steps; NaN = missing) and mask uint8 [B, S, 6] or None.
+    Returns (e2 fp64 [S-1, B, n], pair_ok int32 [S-1, B], r2 fp64 [S, B, 6], seen int32 [S, B])."""
+    mode, S, B, n, K, dev = _em_head("ukf_em_stats", mode, mean_s, cov_s, alive)
+    dt_ = prop_em.dtype
+    _need_real(dt_)
+    if tuple(prop_em.shape) != (S - 1, B * K, 6) or prop_em.device != dev or not prop_em.is_contiguous():
+        raise HodeError(f"ukf_em_stats: prop_em must be a contiguous [S-1, B*K, 6] with K = 2 n + 1 = {K}")
+    if tuple(obs.shape) != (B, S, 6) or obs.dtype != dt_ or obs.device != dev or not obs.is_contiguous():
+        raise HodeError("ukf_em_stats: obs must be a contiguous [B, S, 6] of prop_em's dtype")
+    if mask is not None and (tuple(mask.shape) != (B, S, 6) or mask.dtype != torch.uint8 or mask.device != dev or not mask.is_contiguous()):
+        raise HodeError("ukf_em_stats: mask must be a contiguous uint8 [B, S, 6] or None")
+    _need_vectors("ukf_em_stats", dev, torch.int32, (("status", status, (S - 1) * B * K),))
+    _need_vectors("ukf_em_stats", dev, torch.float64, (("chol", chol, (S - 1) * B * n * n), ("gain", gain, (S - 1) * B * n * n),
+                                                       ("moments", moments, S * B * 12)))
+    shapes = (((S - 1, B, n), torch.float64), ((S - 1, B), torch.int32), ((S, B, 6), torch.float64), ((S, B), torch.int32))
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=d, device=dev) for sh, d in shapes)
+    if len(out) != 4 or not all(_is_buffer(t, d, dev, sh) for t, (sh, d) in zip(out, shapes)):
+        raise HodeError("ukf_em_stats: out must be (e2 fp64 [S-1, B, n], pair_ok int32 [S-1, B], r2 fp64 [S, B, 6], seen int32 [S, B]), "
+                        "contiguous on the device")
+    _em_distinct("ukf_em_stats", (prop_em, status, chol, mean_s, cov_s, gain, alive, obs, mask, moments), out)
+    gamma, wm0, wc0, wi = (float(v) for v in weights)
+    _call("ukf_em_stats", dt_, S, B, int(link), (C.c_int32 * PF_MAX_AUX)(*mode), gamma, wm0, wc0, wi, prop_em, status, chol, mean_s, cov_s,
+          gain, alive, obs, mask, moments, *out)
+    return tuple(out)
+
+
+def ukf_em_mstep(e2, pair_ok, r2, seen, dt, q, walk, sigma, mode, fit_mask, floor, link=1, sums=None, check_dt=True):
+    """Reduce one E-step and update the noise IN PLACE (include/hode_ukf_em.h): e2 fp64 [S-1, B, n], pair_ok int32 [S-1, B],
+    r2 fp64 [S, B, 6], seen int32 [S, B] as ukf_em_stats gave them, dt fp64 [S, B] (row 0 is not read); q fp64 [6], walk fp64 [17],
+    sigma fp64 [6] on the device; mode, fit_mask (29 flags: q, walk by column, sigma) and floor (29 values >= 0) on the HOST.
+    check_dt: read dt back once and refuse a dt <= 0 past row 0 (a caller that knows its grid passes False).
+    Returns sums fp64 [37] (UKF_EM_SUM_AT): A by coordinate, N, D, R, M."""
+    _need_gpu(r2)
+    mode = [int(v) for v in (mode.tolist() if hasattr(mode, "tolist") else mode)]
+    if len(mode) != PF_MAX_AUX or any(v not in (0, 1, 2) for v in mode):
+        raise HodeError(f"ukf_em_mstep: mode must be {PF_MAX_AUX} host integers in 0..2 (PF_MOVE)")
+    n = 6 + sum(1 for v in mode if v)
+    if r2.dim() != 3 or r2.shape[2] != 6 or r2.shape[0] < 1 or r2.shape[1] < 1:
+        raise HodeError("ukf_em_mstep: r2 must be [S, B, 6] with S >= 1, B >= 1")
+    S, B, dev = int(r2.shape[0]), int(r2.shape[1]), r2.device
+    fit_mask = [int(bool(v)) for v in (fit_mask.tolist() if hasattr(fit_mask, "tolist") else fit_mask)]
+    floor = [float(v) for v in (floor.tolist() if hasattr(floor, "tolist") else floor)]
+    if len(fit_mask) != UKF_EM_FIT or len(floor) != UKF_EM_FIT or not all(0.0 <= v < float("inf") for v in floor):
+        raise HodeError(f"ukf_em_mstep: fit_mask and floor must hold {UKF_EM_FIT} host values (q [6], walk [17], sigma [6]), floor >= 0")
+    _need_vectors("ukf_em_mstep", dev, torch.float64, (("e2", e2, (S - 1) * B * n), ("r2", r2, S * B * 6), ("dt", dt, S * B), ("q", q, 6),
+                                                       ("walk", walk, PF_MAX_AUX), ("sigma", sigma, 6)))
+    _need_vectors("ukf_em_mstep", dev, torch.int32, (("pair_ok", pair_ok, (S - 1) * B), ("seen", seen, S * B)))
+    if sums is None:
+        sums = torch.empty(UKF_EM_SUMS, dtype=torch.float64, device=dev)
+    if not _is_buffer(sums, torch.float64, dev, numel=UKF_EM_SUMS):
+        raise HodeError(f"ukf_em_mstep: sums must be a contiguous fp64 [{UKF_EM_SUMS}] on the device")
+    _em_distinct("ukf_em_mstep", (e2, pair_ok, r2, seen, dt), (q, walk, sigma, sums))
+    if check_dt and S > 1 and not bool((dt.view(S, B)[1:] > 0).all()):
+        raise HodeError("ukf_em_mstep: every dt past row 0 must be positive")
+    _call("ukf_em_mstep", None, S, B, int(link), (C.c_int32 * PF_MAX_AUX)(*mode), (C.c_int32 * UKF_EM_FIT)(*fit_mask),
+          (C.c_double * UKF_EM_FIT)(*floor), e2, pair_ok, r2, seen, dt, q, walk, sigma, sums)
+    return sums
+
+
 PRED_MAX_BINS, PRED_FIXED_COLS, PRED_SCORE_BLOCKS = 32, 16, 128
 PRED_STATE = ("n", "mean", "m2", "pit", "lmax", "lsum")
 

@@ -25,14 +25,14 @@ from .initial_state import InitialStatePrior, LatentStateResult
 from .population import PopulationResult, run_population
 from .predictive import LooResult, PredictiveAccumulator, PredictiveSummary, compare, loo_tail_size, predictive_summary, tail_size
 from .sobol import SobolIndices, saltelli_design, sobol_indices, sobol_study
-from .ukf import UKFResult, UKFSmoothResult, run_ukf
+from .ukf import UKFNoiseFit, UKFResult, UKFSmoothResult, fit_ukf_noise, run_ukf
 from .vi import VariationalInference
 
 __all__ = ["VariationalInference", "fit_patients", "CalibrationResult", "run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results",
            "sobol_study", "sobol_indices", "saltelli_design", "SobolIndices", "PredictiveAccumulator", "PredictiveSummary", "predictive_summary",
            "tail_size", "loo_tail_size", "LooResult", "compare", "run_population", "PopulationResult", "InitialStatePrior",
            "LatentStateResult", "run_filter", "FilterResult", "SmoothResult", "ParameterLearning", "LearnedParameters", "run_ukf",
-           "UKFResult", "UKFSmoothResult"]
+           "UKFResult", "UKFSmoothResult", "fit_ukf_noise", "UKFNoiseFit"]
 
 _MCMC_NAMES = ("run_nuts", "compute_ess", "posterior_summary", "save_mcmc_results", "load_mcmc_results")
 _HERE = os.path.dirname(os.path.abspath(__file__))
